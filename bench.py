@@ -1,17 +1,18 @@
 """bench.py -- the BASELINE.json metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input: BASELINE.json configs[1], the C-ViViT tokenizer
 (dim 512, patch 32, temporal patch 2, depth 4+4, LFQ 65 536) encoding a (8, 3, 17, 256, 256) f32 video that is already
 resident in HBM into (8, 9, 8, 8) int64 token ids, bf16 MFMA operands / f32 accumulation.  With N > 1 every rank encodes
-its own 8 videos (batch sharding, weak scaling, no collective on the data path).  The timed region is K steps bracketed by
-barrier + synchronize; it is repeated `--groups` times and the MEDIAN group is reported (a 20-step region is 20 ms: one
-scheduling hiccup would move a single region by several per cent), max over ranks.  The steps rotate through `--rotate`
-distinct input batches (3 x 107 MB > the 256 MB Infinity Cache) so the video really comes from HBM.
+its own 8 videos (batch sharding, weak scaling, no collective on the data path).  After W warm-up steps, exactly K steps are
+timed as one region bracketed by barrier + synchronize (max over ranks); ms_per_step is that region over K.  The steps rotate
+through `--rotate` distinct input batches (3 x 107 MB > the 256 MB Infinity Cache) so the video really comes from HBM.
+`--dump-outputs DIR` writes the token ids of the last timed step to DIR/ids.npy (float64; seeded inputs and weights, so two
+builds can be compared output for output).
 
-The same JSON line carries
+A plain run does only the headline and prints its JSON line.  With `--full` the same JSON line also carries
   roofline     : the encode leg's dominant kernel -- algorithmic flops per launch over its live HIP-event duration, plus the
                  fabric traffic per launch from the committed rocprofv3 PMC passes (profiles/pmc_traffic_rNN.json);
   kernels      : every kernel of the encode / decode / sampling legs against ITS roofline (HBM GB/s for the patch / VQ /
@@ -28,6 +29,7 @@ The same JSON line carries
                  its reconstruction loss (SURVEY.md 8f rows 1 and 4);
   cpu_baseline : the CPU oracle (a port of the reference algorithm, oracle/phenaki_oracle.py) on a bounded sample of
                  the same workload on this box's host cores.
+--no-sample / --no-cpu / --no-parity-mode / --no-kernels / --encode-only / --legs / --groups select among these and only act with --full.
 """
 import argparse
 import json
@@ -55,7 +57,9 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--groups', type=int, default=25, help='timed regions of --steps steps; the median is reported')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the token ids of the last timed step to DIR/ids.npy (float64)')
+    ap.add_argument('--full', action='store_true', help='also run the legs, per-kernel rooflines, parity modes and CPU baseline')
+    ap.add_argument('--groups', type=int, default=25, help='--full: timed regions of the decode / encode_b32 / parity-mode legs (median reported)')
     ap.add_argument('--rotate', type=int, default=3, help='distinct input batches the steps rotate through')
     ap.add_argument('--batch', type=int, default=8, help='videos per GPU (configs[1]: 8)')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
@@ -64,12 +68,15 @@ def parse():
     ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
     ap.add_argument('--no-parity-mode', action='store_true', help='skip the exact-f32 timing')
     ap.add_argument('--no-kernels', action='store_true', help='skip the per-kernel roofline table')
-    ap.add_argument('--encode-only', action='store_true', help='only the headline leg (profiling runs)')
+    ap.add_argument('--encode-only', action='store_true', help='--full: only the headline leg and its kernel table (profiling runs)')
     ap.add_argument('--legs', default='decode,encode_b32,sample,sample_cfg3,sample_b32,make_video,scaling_projection,objective,train_step,cvivit_train_step,cvivit_gan_step',
                     help='comma list of the legs reported beside the headline encode leg')
     ap.add_argument('--sample-batch', type=int, default=8)
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def _free_port():
@@ -83,7 +90,8 @@ def _free_port():
 
 def spawn_ranks_if_needed(args):
     """`python bench.py --gpus N` (N > 1, no launcher): start the N ranks ourselves -- one process per GPU under
-    torch.distributed.run, RCCL over xGMI -- by replacing this process, so the single JSON line still comes from rank 0 on stdout.
+    torch.distributed.run, RCCL over xGMI -- as a child process whose exit status this one returns, so the single JSON line still comes from
+    rank 0 on stdout.  (A child, not exec: device_count() may already have opened the HIP runtime in this process.)
     Under a launcher (WORLD_SIZE set) this is a no-op.  Fewer than N visible devices is an error, never a silent 1-rank run."""
     if args.gpus <= 1 or 'WORLD_SIZE' in os.environ:
         return
@@ -97,7 +105,8 @@ def spawn_ranks_if_needed(args):
            '--master-port', str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def init_dist(n):
@@ -444,7 +453,9 @@ def roofline_of(rows, dtype, with_traffic=True, section=None):
 
 # ------------------------------------------------------------------------------------------ legs
 
-def bench_encode(cv, args, ws, want_kernels, leg='encode'):
+def bench_encode(cv, args, ws, want_kernels, leg='encode', groups=None):
+    """`groups` (default args.groups) timed regions of args.steps steps; returns (region times, hipGraph used, kernel rows, token ids of the
+    last timed step)"""
     B, R = args.batch, max(1, args.rotate)
     rank = int(os.environ.get('RANK', 0))
     videos = [synthetic_video(B, 17, 256, seed=7 * rank + i).cuda() for i in range(R)]
@@ -462,21 +473,25 @@ def bench_encode(cv, args, ws, want_kernels, leg='encode'):
                 torch.cuda.synchronize()
                 if i == 0:
                     assert torch.equal(out, ids0), 'graph replay changed the token ids'
-                replays.append(rp)
+                replays.append(lambda rp=rp, out=out: (rp(), out)[1])          # a replay refills the captured output tensor
             steps_fn, used_graph = replays, True
         except Exception as e:                     # noqa: BLE001  (recorded in the JSON, never silent)
             print(f'[bench] hipGraph capture failed ({type(e).__name__}: {e}); running eagerly', file=sys.stderr)
             torch.cuda.synchronize()
-    step = lambda i: steps_fn[i % R]()
+    last = [None]
+
+    def step(i):
+        last[0] = steps_fn[i % R]()
     for i in range(args.warmup):
         step(i)
-    times = timed_groups(step, args.steps, args.groups, ws)
+    times = timed_groups(step, args.steps, args.groups if groups is None else groups, ws)
+    ids = last[0].clone()
     rows = None
     if want_kernels:
         with KernelProfiler(leg, args.dtype) as prof:
             cv(videos[0], return_only_codebook_ids=True)
         rows = prof.table()
-    return times, used_graph, rows
+    return times, used_graph, rows, ids
 
 
 def bench_encode_big(cv, args, ws, B, want_kernels):
@@ -484,7 +499,7 @@ def bench_encode_big(cv, args, ws, B, want_kernels):
     import copy
     a = copy.copy(args)
     a.batch, a.rotate, a.groups, a.steps = B, 2, max(5, args.groups // 3), max(5, args.steps // 2)
-    times, used_graph, rows = bench_encode(cv, a, ws, want_kernels, leg=f'encode_b{B}')
+    times, used_graph, rows, _ = bench_encode(cv, a, ws, want_kernels, leg=f'encode_b{B}')
     med = statistics.median(times)
     out = dict(metric='cvivit_encode_frames_per_sec', value=B * 17 * a.steps * ws / med, unit='frames/s', ms_per_step=med / a.steps * 1e3,
                batch_per_gpu=B, token_rows_per_step=B * 576, hip_graph=used_graph, groups=a.groups, steps=a.steps,
@@ -863,7 +878,7 @@ def bench_parity_mode(args, ws, mode='bf16x3'):
     a = copy.copy(args)
     a.dtype, a.groups, a.no_graph = mode, max(5, args.groups // 5), args.no_graph
     cv, mg, cr, ph = build_models(mode, not args.no_sample)
-    times, used_graph, rows = bench_encode(cv, a, ws, True)
+    times, used_graph, rows, _ = bench_encode(cv, a, ws, True)
     med = statistics.median(times)
     out = dict(dtype={'fp32': 'f32'}.get(mode, mode), metric='cvivit_encode_frames_per_sec', value=a.batch * 17 * a.steps * ws / med, unit='frames/s',
                ms_per_step=med / a.steps * 1e3, hip_graph=used_graph, roofline=roofline_of(rows, mode, with_traffic=mode == 'bf16x3', section='bf16x3_encode'),
@@ -1010,12 +1025,12 @@ def main():
     if rank == 0:
         build()
     barrier_sync(ws)
-    sampler = not (args.no_sample or args.encode_only)
+    sampler = args.full and not (args.no_sample or args.encode_only)
     cv, mg, cr, ph = build_models(args.dtype, sampler)
     want_k = not (args.no_kernels or args.encode_only)
 
-    times, used_graph, enc_rows = bench_encode(cv, args, ws, want_k or not args.no_kernels)
-    med = statistics.median(times)
+    times, used_graph, enc_rows, ids = bench_encode(cv, args, ws, args.full and not args.no_kernels, groups=1)
+    med = times[0]
     frames = args.batch * 17 * args.steps * ws
     result = {
         'metric': 'cvivit_encode_frames_per_sec', 'value': frames / med, 'unit': 'frames/s', 'n_gpus': ws,
@@ -1025,9 +1040,22 @@ def main():
                                f'video -> token ids, ({args.batch},3,17,256,256) f32 per GPU resident in HBM',
                    'global_batch': args.batch * ws, 'frames_per_video': 17, 'parallelism': f'batch-shard x{ws}, no data-path collective',
                    'hip_graph': used_graph, 'input_rotation': f'{args.rotate} distinct batches ({args.rotate * args.batch * 13.37:.0f} MB) per GPU',
-                   'timing': f'median of {args.groups} regions of {args.steps} steps (min {min(times) / args.steps * 1e3:.4f}, '
-                             f'max {max(times) / args.steps * 1e3:.4f} ms/step), total timed {sum(times):.2f} s'},
+                   'timing': f'one region of {args.steps} steps after {args.warmup} warm-up steps, {med:.4f} s'},
     }
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = 'ids' if ws == 1 else f'ids_rank{rank}'
+        np.save(os.path.join(args.dump_outputs, name + '.npy'), ids.cpu().numpy().astype(np.float64))
+    if not args.full:
+        if rank == 0:
+            line = {k: v for k, v in compact_line(result).items() if k != 'full_report'}         # a plain run writes no full report
+            print(json.dumps(line, separators=(',', ':')))
+            sys.stdout.flush()
+        if ws > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
     kernels = []
     if enc_rows:
         result['roofline'] = roofline_of(enc_rows, args.dtype)

@@ -660,6 +660,30 @@ def keys_golden(R):
     print('state_dict_keys.json written')
 
 
+def mp4_golden():
+    """the reference's MP4 helpers (data.py:128-181) on tests/test_host.py's lossless in-memory cv2 stand-in: the uint8 frames its
+    tensor_to_video writes for the test clip, and what its video_to_tensor reads back under each of the test's keyword sets"""
+    import ast
+    from tests.test_host import _MP4_READS, _FakeCv2, _fake_cv2, _mp4_clip
+    src = os.path.join(ref_shim.REFERENCE_ROOT, 'phenaki_pytorch', 'data.py')
+    tree = ast.parse(open(src).read())
+    # only these functions are executed from its source (its module-level torchvision import is not needed by them)
+    keep = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in ('video_to_tensor', 'tensor_to_video', 'crop_center', 'exists', 'pair')]
+    sys.modules['cv2'] = _fake_cv2()
+    try:
+        ns = {}
+        exec('import cv2, torch\nimport numpy as np\nfrom einops import rearrange\n', ns)
+        exec(compile(ast.Module(body=keep, type_ignores=[]), src, 'exec'), ns)
+        ns['tensor_to_video'](_mp4_clip(), 'mem://ref.mp4')
+        reads = [(kw, ns['video_to_tensor']('mem://ref.mp4', **kw)) for kw in _MP4_READS]
+    finally:
+        del sys.modules['cv2']
+    assert all(torch.equal(t, t.round().clamp(0, 255)) for _, t in reads)
+    frames = torch.stack([torch.from_numpy(f) for f in _FakeCv2.store['mem://ref.mp4']])
+    torch.save(dict(frames=frames, reads=[(kw, t.to(torch.uint8)) for kw, t in reads]), os.path.join(OUT, 'mp4_helpers.pt'))
+    print('mp4_helpers.pt written')
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     R = ref_shim.load()
@@ -692,6 +716,8 @@ def main():
     if 'tiny' in which or 'critics' in which:
         selfcritic_golden(R, TINY, tag='tiny')
         unconditional_golden(R, TINY, tag='tiny')
+    if 'tiny' in which or 'mp4' in which:
+        mp4_golden()
     if 'tiny' in which or 'make_video' in which:
         make_video_golden(R, TINY, frames=(5, 4, 4), prime_lengths=3, ctx_lens=(5, 7, 4), tag='tiny', keep_videos=True)
         make_video_golden(R, TINY, frames=(5, 4, 6), prime_lengths=(3, 1), ctx_lens=(6, 3, 8), tag='tiny_perscene', keep_videos=True)

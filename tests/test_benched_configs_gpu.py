@@ -202,3 +202,33 @@ def test_sample_b32_one_teacher_forced_step_matches_oracle(dtype, mtol):
     if dtype in F32_GRADE:
         assert flips <= 4, f'{dtype}: {flips} audited near ties in one forced step at B = 32'
     record_parity('sample_b32_teacher_forced_vs_oracle', dict(dtype=dtype, batch=32, steps_bit_identical=exact, of=1, audited_argmax_flips=flips))
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_ids(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`: the headline alone, K timed steps behind ms_per_step, and DIR/ids.npy holding the token ids of
+    the last timed step -- the ids CViViT.forward(video, return_only_codebook_ids=True) returns for that step's input batch."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps = 4
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    assert d['metric'] == 'cvivit_encode_frames_per_sec' and d['unit'] == 'frames/s' and d['higher_is_better'] and d['dtype'] == 'bf16'
+    assert d['steps'] == steps and d['ms_per_step'] > 0
+    assert abs(d['value'] - 8 * 17 / (d['ms_per_step'] * 1e-3)) < 1e-3 * d['value']            # the line rounds ms_per_step to 0.1 us
+    assert not {'roofline', 'kernels', 'sample', 'legs', 'parity', 'cpu_baseline', 'full_report'} & set(d), 'a plain run is the headline only'
+    ids = np.load(os.path.join(str(tmp_path), 'ids.npy'))
+    assert ids.dtype == np.float64 and ids.shape == (8, 9, 8, 8)
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    cv = bench.build_models('bf16', False)[0]
+    video = bench.synthetic_video(8, 17, 256, seed=(steps - 1) % 3).cuda()            # the steps rotate through 3 input batches
+    want = cv(video, return_only_codebook_ids=True).cpu().numpy().astype(np.float64)
+    assert np.array_equal(ids, want), f'{int((ids != want).sum())} of {ids.size} dumped ids differ from a direct encode of the same batch'

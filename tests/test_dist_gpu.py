@@ -100,7 +100,7 @@ def test_bench_gpus2_launches_two_ranks_by_itself(tmp_path):
     if not two:
         env['PK_BENCH_ONE_DEVICE'] = '1'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--groups', '2', '--batch', '2',
-                        '--sample-batch', '1', '--no-cpu', '--no-parity-mode', '--no-kernels', '--no-graph', '--legs', 'sample'],
+                        '--sample-batch', '1', '--full', '--no-cpu', '--no-parity-mode', '--no-kernels', '--no-graph', '--legs', 'sample'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -129,7 +129,7 @@ def test_bench_gpus8_whole_flow_on_one_device(tmp_path):
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--groups', '2', '--batch', '1',
-                        '--sample-batch', '4', '--no-cpu', '--no-parity-mode', '--no-kernels', '--no-graph', '--legs', 'sample,make_video'],
+                        '--sample-batch', '4', '--full', '--no-cpu', '--no-parity-mode', '--no-kernels', '--no-graph', '--legs', 'sample,make_video'],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])          # the compact line the driver parses

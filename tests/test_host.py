@@ -503,21 +503,33 @@ class _FakeCv2:
         pass
 
 
-def test_mp4_helpers_match_the_reference_on_a_lossless_stand_in_codec(monkeypatch):
-    """SURVEY.md 8f row 4 (video I/O): video_to_tensor / tensor_to_video (reference data.py:128-181) go through OpenCV, which this image lacks.
-    With an in-memory cv2 stand-in both implementations -- the product's and, where /root/reference exists, the reference's own functions
-    loaded from its data.py -- write and read the same clip: identical tensors, incl. the reference's quirks (the last decoded frame is
-    dropped, `[:num_frames]` with the default -1 drops one more, crop_size crops the centre, values stay 0..255 in OpenCV's channel order)."""
+# the clip and the read-back keyword sets of the MP4 test; oracle/make_golden.py (`mp4`) ran the reference's helpers on exactly these
+_MP4_READS = (dict(), dict(num_frames=3), dict(num_frames=100, crop_size=16), dict(crop_size=(20, 10)))
+
+
+def _mp4_clip():
+    g = torch.Generator().manual_seed(11)
+    return torch.randint(0, 256, (3, 7, 24, 40), generator=g).float()
+
+
+def _fake_cv2():
     import importlib.machinery
     import types
     fake = types.ModuleType('cv2')
     fake.__spec__ = importlib.machinery.ModuleSpec('cv2', None)
     for k in ('VideoWriter_fourcc', 'VideoWriter', 'VideoCapture', 'destroyAllWindows'):
         setattr(fake, k, getattr(_FakeCv2, k))
-    monkeypatch.setitem(sys.modules, 'cv2', fake)
+    return fake
+
+
+def test_mp4_helpers_match_the_reference_on_a_lossless_stand_in_codec(monkeypatch, golden_dir):
+    """SURVEY.md 8f row 4 (video I/O): video_to_tensor / tensor_to_video (reference data.py:128-181) go through OpenCV, which this image lacks.
+    With an in-memory cv2 stand-in the product's functions write and read the clip as the reference's own functions did on the same stand-in
+    (tests/golden/mp4_helpers.pt): identical frames and tensors, incl. the reference's quirks (the last decoded frame is dropped,
+    `[:num_frames]` with the default -1 drops one more, crop_size crops the centre, values stay 0..255 in OpenCV's channel order)."""
+    monkeypatch.setitem(sys.modules, 'cv2', _fake_cv2())
     from phenaki_pytorch_amd import data as D
-    g = torch.Generator().manual_seed(11)
-    clip = torch.randint(0, 256, (3, 7, 24, 40), generator=g).float()
+    clip = _mp4_clip()
     D.tensor_to_video(clip, 'mem://a.mp4')
     assert len(_FakeCv2.store['mem://a.mp4']) == 7
     full = D.video_to_tensor('mem://a.mp4', num_frames=100)
@@ -525,20 +537,11 @@ def test_mp4_helpers_match_the_reference_on_a_lossless_stand_in_codec(monkeypatc
     assert tuple(D.video_to_tensor('mem://a.mp4').shape) == (3, 5, 24, 40)                          # default num_frames = -1: `[:, :-1]`
     crop = D.video_to_tensor('mem://a.mp4', num_frames=4, crop_size=16)
     assert tuple(crop.shape) == (3, 4, 16, 16) and torch.equal(crop, clip[:, :4, 4:20, 12:28])
-    ref_root = os.environ.get('PHENAKI_REFERENCE_ROOT', '/root/reference')
-    src = os.path.join(ref_root, 'phenaki_pytorch', 'data.py')
-    if os.path.exists(src):
-        # the reference's own two functions, executed from its source with the stand-in cv2 (its module-level torchvision import is not needed by them)
-        import ast
-        tree = ast.parse(open(src).read())
-        keep = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in ('video_to_tensor', 'tensor_to_video', 'crop_center', 'exists', 'pair')]
-        ns = {}
-        exec('import cv2, torch\nimport numpy as np\nfrom einops import rearrange\n', ns)
-        exec(compile(ast.Module(body=keep, type_ignores=[]), src, 'exec'), ns)
-        ns['tensor_to_video'](clip, 'mem://ref.mp4')
-        assert all((a == b).all() for a, b in zip(_FakeCv2.store['mem://ref.mp4'], _FakeCv2.store['mem://a.mp4']))
-        for kw in (dict(), dict(num_frames=3), dict(num_frames=100, crop_size=16), dict(crop_size=(20, 10))):
-            assert torch.equal(ns['video_to_tensor']('mem://ref.mp4', **kw), D.video_to_tensor('mem://a.mp4', **kw)), kw
+    ref = torch.load(os.path.join(golden_dir, 'mp4_helpers.pt'))
+    assert torch.equal(torch.stack([torch.from_numpy(f) for f in _FakeCv2.store['mem://a.mp4']]), ref['frames'])
+    assert [kw for kw, _ in ref['reads']] == list(_MP4_READS)
+    for kw, want in ref['reads']:
+        assert torch.equal(D.video_to_tensor('mem://a.mp4', **kw), want.float()), kw
 
 
 def _has(mod):

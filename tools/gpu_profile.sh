@@ -10,9 +10,9 @@ rm -rf $P; mkdir -p $P
 echo "== kernel trace: encode leg"; date
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $P/enc -o enc -- python bench.py --encode-only --groups 3 --steps 20 --warmup 3 > $P/enc.json 2> $P/enc.err; echo rc=$?
 echo "== kernel trace: whole bench (no cpu / parity mode)"; date
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/all -o all -- python bench.py --no-cpu --no-parity-mode --no-kernels --groups 3 --legs decode,sample,sample_cfg3,make_video,objective > $P/all.json 2> $P/all.err; echo rc=$?
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/all -o all -- python bench.py --full --no-cpu --no-parity-mode --no-kernels --groups 3 --legs decode,sample,sample_cfg3,make_video,objective > $P/all.json 2> $P/all.err; echo rc=$?
 echo "== kernel trace: training legs (Phenaki step in bf16x3 + bf16, tokenizer step, tokenizer GAN step)"; date
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/train -o train -- python bench.py --no-cpu --no-parity-mode --no-kernels --groups 2 --legs train_step,cvivit_train_step,cvivit_gan_step > $P/train.json 2> $P/train.err; echo rc=$?
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P/train -o train -- python bench.py --full --no-cpu --no-parity-mode --no-kernels --groups 2 --legs train_step,cvivit_train_step,cvivit_gan_step > $P/train.json 2> $P/train.err; echo rc=$?
 echo "== steady-state launch census of the Phenaki training step (bf16x3; tools/train_census.py)"; date
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$P/census -o c -- python $OLDPWD/tools/train_census.py bf16x3 6 phenaki > $OLDPWD/$P/census.log 2>&1 ); echo rc=$?
 python tools/train_census.py --summary $P/census 6 > $P/train_step_census_$R.txt; head -12 $P/train_step_census_$R.txt
@@ -23,7 +23,7 @@ timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/
 # per-leg sections (no null roofline.traffic): the bf16 sampling leg, and the parity-grade bf16x3 mode's encode / sampling legs
 pmc_pass() {   # name counter args...
   local name=$1 ctr=$2; shift 2
-  timeout 600 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $P/$name -o p -- python bench.py --no-graph --no-kernels --no-cpu --no-parity-mode --groups 1 --steps 2 --warmup 1 "$@" > /dev/null 2> $P/$name.err; echo "$name rc=$?"
+  timeout 600 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $P/$name -o p -- python bench.py --full --no-graph --no-kernels --no-cpu --no-parity-mode --groups 1 --steps 2 --warmup 1 "$@" > /dev/null 2> $P/$name.err; echo "$name rc=$?"
 }
 echo "== PMC sample leg (bf16)"; date
 pmc_pass pmc_s_fetch FETCH_SIZE --legs sample

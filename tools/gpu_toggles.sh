@@ -2,13 +2,14 @@
 # same-box effect of each round-2 switch on every bench leg (working tree; one switch turned off at a time), old tree for reference
 set -u
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+OUT=${OUT:-$PWD/bench_out}
+mkdir -p $OUT
 run() {  # name dir env...
   name=$1; dir=$2; shift 2
-  (cd $dir && env "$@" timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-parity-mode --no-kernels --no-graph --groups 7 2>/dev/null) > gpurun_out/tg_$name.json
+  (cd $dir && env "$@" timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-parity-mode --no-kernels --no-graph --groups 7 2>/dev/null) > $OUT/tg_$name.json
   python - <<PY
 import json
-d=json.load(open('gpurun_out/tg_$name.json')); print(f"{'$name':22s}", 'encode ms', round(d['ms_per_step'],4), 'decode', round(d['decode'].get('ms_per_step'),4), 'sample', round(d['sample']['seconds_per_sample_call'],5), 'cfg3', round(d['sample_cfg3']['seconds_per_sample_call'],5), 'mv', round(d['make_video']['wall_clock_s'],4))
+d=json.load(open('$OUT/tg_$name.json')); print(f"{'$name':22s}", 'encode ms', round(d['ms_per_step'],4), 'decode', round(d['decode'].get('ms_per_step'),4), 'sample', round(d['sample']['seconds_per_sample_call'],5), 'cfg3', round(d['sample_cfg3']['seconds_per_sample_call'],5), 'mv', round(d['make_video']['wall_clock_s'],4))
 PY
 }
 [ -d tools/_bin/old ] && run old tools/_bin/old X=1

@@ -7,7 +7,7 @@ for which in old new; do
   if [ $which = old ]; then dir=$PWD/tools/_bin/old; else dir=$PWD; fi
   out=$PWD/gpurun_out/trace_ab/$which
   rm -rf $out; mkdir -p $out
-  (cd $dir && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o t -- python bench.py --steps 20 --warmup 5 --no-cpu --no-parity-mode --no-kernels --no-graph --groups 3 > $out/bench.json 2> $out/err.txt)
+  (cd $dir && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o t -- python bench.py --full --steps 20 --warmup 5 --no-cpu --no-parity-mode --no-kernels --no-graph --groups 3 > $out/bench.json 2> $out/err.txt)
   find $out -name "*kernel_trace.csv" -delete; find $out -name "*.db" -delete
 done
 python - <<'PY'
