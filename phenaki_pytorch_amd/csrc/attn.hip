@@ -138,8 +138,8 @@ struct AttnArgs {
     // needed: ~40 % of the VALU work of a key tile.  An integer shift of the exponent leaves every mantissa -- hence the bf16
     // rounding of p -- independent of the tiling.  off2 < 0: running-max softmax.
     float off2;
-    // training forward (LDS-free kernel only): lse[(s h + hh) nq + i] = log sum_j exp(score[i][j]) for the backward kernels (round 6: they recomputed
-    // it with one extra pass over the keys); null: not written
+    // training forward (the LDS-free kernel and the split-bf16 LDS-staged running-max kernel): lse[(s h + hh) nq + i] = log sum_j exp(score[i][j])
+    // for the backward kernels (round 6: they recomputed it with one extra pass over the keys); null: not written
     float* lse;
 };
 
@@ -469,12 +469,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
             }
     };
 
-    const T* Qp = reinterpret_cast<const T*>(p.Qp) + ((size_t)sh * p.nq_pad + (active ? q0 : 0)) * DH;
+    // Q fragment rows are clamped to the head's image: with 48 rows per wave (QF = 3) the last wave of a head reaches past nq_pad whenever
+    // nq_pad % 48 != 0 (n = 320: rows 320..335), i.e. into the next head's rows or, for the last (s, h), past the allocation
+    const T* Qp = reinterpret_cast<const T*>(p.Qp) + (size_t)sh * p.nq_pad * DH;
     Frag<T> fq[QF][2];
 #pragma unroll
-    for (int qf = 0; qf < QF; ++qf)
+    for (int qf = 0; qf < QF; ++qf) {
+        const int qr = active ? q0 + qf * 16 + lr : lr;
+        const int qc = qr < p.nq_pad ? qr : p.nq_pad - 1;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) frag_load(fq[qf][c], Qp + (size_t)(qf * 16 + lr) * DH + c * 32 + g * 8);
+        for (int c = 0; c < 2; ++c) frag_load(fq[qf][c], Qp + (size_t)qc * DH + c * 32 + g * 8);
+    }
 
     float m[QF], l[QF];
     f32x4 o[QF][4], lsum[QF];
@@ -1061,8 +1066,10 @@ extern "C" int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void
     return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, bias_tab, tab_len,
                          pos_code, code_off, tab_run4, score_bound, nullptr, stream);
 }
-// the training forward: the same product through the LDS-free kernel, which also writes lse (S h, nq) = the log-sum-exp of every score row --
-// pk_attn_bwd (flags bit 1) then skips its own pass over the keys for it.  No bias table / fixed-offset form here.
+// the training forward: the same product, which also writes lse (S h, nq) = the log-sum-exp of every score row -- pk_attn_bwd (flags bit 1) then
+// skips its own pass over the keys for it.  Split-bf16 self-attention without null keys, key mask or causal mask (n >= 128) runs on the LDS-staged
+// kernel in its running-max form (64 or 48 query rows per wave, chosen from the workgroup count and the CU count); every other shape on the
+// LDS-free kernel.  No bias table / fixed-offset form here.
 extern "C" int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const void* Vt,
                                const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                                const float* slopes, int causal, void* O, int ldo, int out_is_f32,

@@ -598,7 +598,8 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
     if (ln_s) {
         // LayerNorm-folded GEMM: LDS-DMA main loop only (the statistics come from its A fragments), vector epilogue, 64x64 / 128x128 tiles
         if (!dma_ok || !v || !al16(ln_s) || !al16(ln_t) || a_rows) return PK_EINVAL;
-        const bool big = variant == 24 || variant == 2 || variant == 9;
+        // 128x128 wherever the automatic choice is a large tile (50: the 256x256 loop, which has no folded form)
+        const bool big = variant == 24 || variant == 2 || variant == 9 || variant == 50;
 #ifdef PK_P8_ABLATE
         if (ln_stats && variant == 50 && dtype != 0) {         // the two-group 256 x 256 loop with the producer's row statistics (measured, not used: see below)
             return dtype == 1 ? launch_p8<bf16, 0, 4, 2>(p, e, a_nrows, s) : launch_p8<bf16x3, 0, 4, 2>(p, e, a_nrows, s);

@@ -857,9 +857,13 @@ extern "C" int pk_peg_bwd(const float* dy, const float* x, const float* wt, floa
     if (part && (dv > 256 || 256 % dv)) return PK_EINVAL;
     hipStream_t s = STREAM(stream);
     const long rows = (long)B * T * H * W, total = rows * dv;
-    // dx: the adjoint stencil on the forward's row kernel where it exists (W in {4, 8, 16}), else the 27-gather kernel
-    if (pk_peg_adjoint(dy, wt, dx, B, T, H, W, D, causal, stream) != PK_OK)
-        hipLaunchKernelGGL(peg_bwd_kernel, dim3(nblocks(total)), dim3(256), 0, s, dy, wt, dx, B, T, H, W, D, causal ? 2 : 1, total);
+    // both dx kernels read dy's neighbours while other threads write dx: no in-place form
+    if (dy == dx) return PK_EINVAL;
+    // dx: the adjoint stencil on the forward's row kernel where it exists (W in {4, 8, 16}), else the 27-gather kernel; an error of the
+    // adjoint is the caller's, never a reason to run the other kernel
+    if (W == 4 || W == 8 || W == 16) {
+        if (int rc = pk_peg_adjoint(dy, wt, dx, B, T, H, W, D, causal, stream)) return rc;
+    } else hipLaunchKernelGGL(peg_bwd_kernel, dim3(nblocks(total)), dim3(256), 0, s, dy, wt, dx, B, T, H, W, D, causal ? 2 : 1, total);
     if (part) {
         const int P = pk_peg_wgrad_parts(rows);
         const int rpb = (int)((rows + P - 1) / P);

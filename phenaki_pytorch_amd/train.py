@@ -165,7 +165,9 @@ class WeightImages:
     """The operand images of a module's projection weights in one compute dtype -- for every Linear both the forward image of W and the image of
     W^T its backward multiplies by -- held in persistent buffers and re-packed by ONE launch per pass (`refresh`, pk_pack_table).  Round 6: the
     training step issued ~220 single-matrix pk_pack launches of 5-9 us for these (every weight twice per step).  The pad rows / columns of an image
-    are zeroed once at allocation and never written again.  Images are tied to the storage of the parameters they were built for (`key`)."""
+    are zeroed once at allocation and never written again.  Images are tied to the parameters they were built for (`param_key`): the key is taken
+    from the module's CURRENT attributes on every call, so a replaced Parameter (`lin.weight = nn.Parameter(...)`, `load_state_dict(assign=True)`)
+    rebuilds the images just like storage moved by `.data = ...` / `.to()`."""
 
     def __init__(self, dtype, device):
         self.dtype, self.device = dtype, device
@@ -180,8 +182,14 @@ class WeightImages:
         """out (R rows): columns [0, K) from src / src^T, zero up to Kp (default: the whole padded row of a full image)"""
         self.jobs.append(L.pack_job(src, R, K, transpose, out, out.shape[-1] if Kp is None else Kp, self.kind))
 
+    @staticmethod
+    def _check(w):
+        assert w.dtype == torch.float32 and w.is_contiguous(), \
+            f'the weight images are packed from contiguous float32 parameters, got {w.dtype} {"contiguous" if w.is_contiguous() else "strided"}'
+
     def both(self, w):
         """w (N, K) -> (image of W: (N, Kp(K)), image of W^T: (K, Kp(N)))"""
+        self._check(w)
         self.live.append(w)
         w = w.detach()
         N, K = w.shape
@@ -194,6 +202,8 @@ class WeightImages:
     def feedforward(self, w1, w2):
         """the GEGLU feed-forward's layouts (see _FFBlock): w1p (2 Fp, Kp(D)) value rows [0, F) | gate rows [Fp, Fp + F); w1t (D, Kp(2 Fp)) its
         transpose; w2 (D, Kp(F)); w2t (Fp, Kp(D)) with zero pad rows"""
+        self._check(w1)
+        self._check(w2)
         self.live += [w1, w2]
         w1, w2 = w1.detach(), w2.detach()
         D, F = w2.shape
@@ -209,9 +219,11 @@ class WeightImages:
         self.params += [w1, w2]
         return dict(w1p=w1p, w1t=w1t, w2=w2f, w2t=w2t)
 
-    def key(self):
-        """storage identity of the LIVE parameters (a `.data = ...` / `.to()` moves them: the job table then points at dead storage)"""
-        return tuple((p.data_ptr(), tuple(p.shape)) for p in self.live)
+    @staticmethod
+    def param_key(params):
+        """identity of the parameter objects AND of their storage: a replaced Parameter, or one whose storage moved (`.data = ...`, `.to()`),
+        leaves the job table pointing at the old storage"""
+        return tuple((id(p), p.data_ptr(), tuple(p.shape), p.dtype, tuple(p.stride())) for p in params)
 
     def refresh(self):
         if len(self.jobs) <= 8:                                          # one block's weights (a direct caller): the jobs travel in the kernel arguments
@@ -226,11 +238,22 @@ class WeightImages:
 _IMAGES = weakref.WeakKeyDictionary()
 
 
+def _transformer_weights(tr):
+    """the projection weights a Transformer's WeightImages are packed from, read from the module's current attributes"""
+    out = []
+    for peg, self_attn, cross_attn, ff in tr.layers:
+        for at in (self_attn, cross_attn):
+            if at is not None:
+                out += [at.to_q.weight, at.to_kv.weight, at.to_out.weight]
+        out += [ff[1].weight, ff[4].weight]
+    return out
+
+
 def transformer_images(tr, dtype):
-    """the WeightImages of a Transformer (attention.py:277-332), built on first use and rebuilt when a parameter's storage changed"""
+    """the WeightImages of a Transformer (attention.py:277-332), built on first use and rebuilt when a parameter was replaced or its storage changed"""
     cache = _IMAGES.setdefault(tr, {})
     wi = cache.get(dtype)
-    if wi is not None and wi._key == wi.key():
+    if wi is not None and wi._key == WeightImages.param_key(_transformer_weights(tr)):
         return wi
     dev = next(tr.parameters()).device
     wi = WeightImages(dtype, dev)
@@ -241,7 +264,8 @@ def transformer_images(tr, dtype):
             rec[name] = None if at is None else dict(wq=wi.both(at.to_q.weight), wkv=wi.both(at.to_kv.weight), wo=wi.both(at.to_out.weight))
         rec['ff'] = wi.feedforward(ff[1].weight, ff[4].weight)
         wi.layers.append(rec)
-    wi._key = wi.key()
+    assert len(wi.live) == len(_transformer_weights(tr))
+    wi._key = WeightImages.param_key(wi.live)
     cache[dtype] = wi
     return wi
 
@@ -250,10 +274,10 @@ def linear_images(lin, dtype):
     """(image of W, image of W^T) of one Linear (the vocabulary head), same caching rule as transformer_images"""
     cache = _IMAGES.setdefault(lin, {})
     wi = cache.get(dtype)
-    if wi is None or wi._key != wi.key():
+    if wi is None or wi._key != WeightImages.param_key([lin.weight]):
         wi = WeightImages(dtype, lin.weight.device)
         wi.pair = wi.both(lin.weight)
-        wi._key = wi.key()
+        wi._key = WeightImages.param_key(wi.live)
         cache[dtype] = wi
     return wi
 

@@ -202,6 +202,56 @@ def test_weight_images_follow_the_parameters(dtype):
     assert torch.equal(y3, yf) and all(torch.equal(g3[k], gf[k]) for k in g3), 'images not rebuilt after the parameters moved to other storage'
 
 
+@pytest.mark.parametrize('dtype', ['fp32', 'bf16x3'])
+def test_weight_images_follow_parameter_replacement(dtype):
+    """a Parameter REPLACED on the module (`lin.weight = nn.Parameter(...)`, `load_state_dict(..., assign=True)`) leaves the old Parameter object --
+    storage and all -- alive in the image table: the images must be keyed on the module's current attributes, not on the objects they were built
+    from, or forward and backward silently run on the old weights.  Non-float32 / strided weights are refused before any image is packed."""
+    import copy
+    from torch import nn
+    import phenaki_pytorch_amd as P
+    from phenaki_pytorch_amd import train as T
+    from phenaki_pytorch_amd.attention import resolve_dtype
+    torch.manual_seed(6)
+    D, S, n = 128, 3, 40
+    tr = P.attention.Transformer(dim=D, depth=2, heads=2, has_cross_attn=True, dim_context=96).cuda()
+    dt = resolve_dtype(dtype)
+    x = torch.randn(S * n, D).cuda()
+    ctx = torch.randn(S * 5, 96).cuda()
+    G = torch.randn(S * n, D).cuda()
+
+    def grads(mod):
+        for p_ in mod.parameters():
+            p_.grad = None
+        xc = x.clone().requires_grad_()
+        with torch.enable_grad():
+            y = T.transformer_train(mod, xc, S, n, dt, context2d=ctx, n_ctx=5)
+        y.backward(G)
+        return {k: v.grad.clone() for k, v in mod.named_parameters() if v.grad is not None}, y.detach()
+
+    def same_as_fresh(what):
+        fresh = copy.deepcopy(tr)
+        g_, y_ = grads(tr)
+        gf, yf = grads(fresh)
+        assert torch.equal(y_, yf) and all(torch.equal(g_[k], gf[k]) for k in g_), f'images not rebuilt after {what}'
+        return y_
+
+    y0 = same_as_fresh('the first pass')
+    at = tr.layers[0][1]
+    at.to_q.weight = nn.Parameter(at.to_q.weight.detach() * 1.5)                     # a new Parameter object on the module
+    tr.layers[1][3][4].weight = nn.Parameter(tr.layers[1][3][4].weight.detach() * 0.5)
+    y1 = same_as_fresh('a Parameter was replaced by assignment')
+    assert not torch.equal(y0, y1)
+    sd = {k: (v * 0.75 if v.ndim == 2 else v.clone()) for k, v in tr.state_dict().items()}
+    tr.load_state_dict(sd, assign=True)                                                # every Parameter replaced
+    y2 = same_as_fresh('load_state_dict(assign=True)')
+    assert not torch.equal(y1, y2)
+    at = tr.layers[0][1]
+    at.to_kv.weight = nn.Parameter(at.to_kv.weight.detach().t().contiguous().t())     # same values, column-major: refused, never packed
+    with pytest.raises(AssertionError, match='contiguous float32'):
+        grads(tr)
+
+
 @pytest.mark.parametrize('dtype,tol', MODES)
 def test_feedforward_block_gradients(dtype, tol):
     """x + FeedForward(x) (attention.py:45-52, inner 1365 -> padded 1368 inside the block) vs torch autograd of the oracle"""
