@@ -22,6 +22,8 @@ def main():
     ap.add_argument('--batch', type=int, default=4)
     ap.add_argument('--dtype', default='bf16x3', choices=['fp32', 'bf16x3', 'bf16'])
     ap.add_argument('--small', action='store_true', help='a small geometry (dim 128, 64 x 64 pixels) instead of the BASELINE one')
+    ap.add_argument('--attn-dropout', type=float, default=0., help='dropout on the attention probabilities of MaskGit and the critic (in training mode)')
+    ap.add_argument('--ff-dropout', type=float, default=0., help='dropout behind GEGLU in their feed-forwards')
     ap.add_argument('--save', default='')
     args = ap.parse_args()
     ws = int(os.environ.get('WORLD_SIZE', '1'))
@@ -34,9 +36,10 @@ def main():
     dim, size, patch, vocab, ctx_dim = (128, 64, 16, 256, 96) if args.small else (512, 256, 32, 65536, 768)
     cvivit = P.CViViT(dim=dim, codebook_size=vocab, image_size=size, patch_size=patch, temporal_patch_size=2, spatial_depth=2 if args.small else 4,
                       temporal_depth=2 if args.small else 4, dim_head=64, heads=dim // 64, use_vgg_and_gan=False)
-    maskgit = P.MaskGit(dim=dim, num_tokens=vocab, max_seq_len=1024, depth=2 if args.small else 6, heads=dim // 64, dim_head=64, dim_context=ctx_dim)
+    maskgit = P.MaskGit(dim=dim, num_tokens=vocab, max_seq_len=1024, depth=2 if args.small else 6, heads=dim // 64, dim_head=64, dim_context=ctx_dim,
+                        attn_dropout=args.attn_dropout, ff_dropout=args.ff_dropout)
     critic = P.TokenCritic(dim=dim, num_tokens=vocab, max_seq_len=1024, depth=2 if args.small else 6, heads=dim // 64, dim_head=64, dim_context=ctx_dim,
-                           has_cross_attn=True)
+                           has_cross_attn=True, attn_dropout=args.attn_dropout, ff_dropout=args.ff_dropout)
     phenaki = P.Phenaki(cvivit=cvivit, maskgit=maskgit, critic=critic, text_embed_dim=ctx_dim).cuda()
     P.set_compute_dtype(phenaki, args.dtype)
     params = list(maskgit.parameters()) + list(critic.parameters())

@@ -257,6 +257,13 @@ int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void* Vt, const
 int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
                     int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
                     int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse, void* stream);
+/* pk_attn_fwd_lse with attn_dropout (attention.py:177; the dropout paragraph further down): the softmax statistics and lse are those of the undropped
+ * probabilities, the P that multiplies V is masked by the keep function of (seed, offset) and O is scaled by `scale`.  Every shape runs on the
+ * LDS-free kernel (the LDS-staged forms serve p = 0 only).  pk_attn_bwd_drop_ws is its backward. */
+int pk_attn_fwd_lse_drop(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
+                         int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
+                         int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse,
+                         unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream);
 /* score_bound: an upper bound of sim + bias over every (head, query, key), or NaN.  q^ and k^ are unit vectors times q_scale / k_scale,
  * so |sim| <= scale * max_d |q_scale_d k_scale_d| and the caller knows the maximum of its bias: with a finite bound (and no key
  * mask, not causal, bf16, >= 64 queries and keys) the softmax numerators are p = 2^(s log2(e) - ceil(bound log2(e))) -- no running
@@ -368,6 +375,20 @@ int pk_layernorm_bwd(const float* x, long long ldx, const float* gamma, const fl
 /* GEGLU on stored pre-activations h (M, >= goff + F): out = h[:, :F] * gelu(h[:, goff : goff + F]) (attention.py:40-43), and its backward */
 int pk_geglu(const float* h, long long ldh, int goff, float* out, long long ldo, int M, int F, void* stream);
 int pk_geglu_bwd(const float* h, long long ldh, int goff, const float* dout, long long ldd, float* dh, long long lddh, int M, int F, void* stream);
+/* ---- dropout of the training kernels (attention.py:45-52 ff_dropout behind GEGLU, attention.py:177 attn_dropout on the softmax probabilities).
+ * A dropout site is a stream (seed, offset); whether element (row, col) of the site survives is a pure function of (seed, offset, row, col)
+ * (csrc/common.hpp drop_keys / drop_row / drop_word / drop_keep; NumPy mirror phenaki_pytorch_amd/dropout.py), so masks are regenerated in the
+ * backward kernels, never stored.  row / col are the factors of the logical element index row * cols + col: attention row = (s heads + h) n + i,
+ * col = j over the nnull + n_kv keys (null keys first); feed-forward row = token row, col over the inner width.  An element is dropped iff its 8-bit
+ * draw < keep_thr (p_eff = keep_thr / 256); survivors are multiplied by `scale`, which the host computes as 1 / (1 - p_eff) in ONE place
+ * (dropout.py quantize).  keep_thr in [1, 256] for the kernels that apply a mask.  Statistically equivalent to torch's nn.Dropout, not its stream.
+ * pk_dropout_mask: out (rows, cols) bytes, 1 = keep, for the index range [0, rows) x [0, cols) (keep_thr in [0, 256]; rows < 2^32).
+ * pk_geglu_drop: out = geglu(h) o m * scale in the pass of pk_geglu; pk_geglu_bwd_drop: dout o m * scale in front of the GEGLU derivative. */
+int pk_dropout_mask(unsigned long long seed, unsigned long long offset, int keep_thr, long long rows, int cols, unsigned char* out, void* stream);
+int pk_geglu_drop(const float* h, long long ldh, int goff, float* out, long long ldo, int M, int F, unsigned long long seed, unsigned long long offset,
+                  int keep_thr, float scale, void* stream);
+int pk_geglu_bwd_drop(const float* h, long long ldh, int goff, const float* dout, long long ldd, float* dh, long long lddh, int M, int F,
+                      unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream);
 /* dz = dy * (y > 0 ? 1 : slope): LeakyReLU backward from the activation's output (position-bias MLP, attention.py:243-247) */
 /* the tokenizer's reconstruction step (cvivit.py:585-591 under autograd; the LFQ's straight-through estimator):
  * pk_scaled_diff: out = (a - b) * scale (* *scale_dev when given) over n floats (n % 4 == 0) -- d/da of (scale / 2) sum (a - b)^2;
@@ -439,6 +460,13 @@ int pk_attn_bwd_work(int S, int heads, int n, int n_kv, int nnull);
 int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long long ldo, int o_bf16, const float* dO, long long lddo,
                    const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
                    float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long long work_floats, void* stream);
+/* pk_attn_bwd_ws behind pk_attn_fwd_lse_drop with the same (seed, offset, keep_thr, scale) (attention.py:177 under autograd): dP = (dO V^T) o m * scale,
+ * dS = P o (dP - D) with D = rowsum(dO o O) of the dropped O, dV = (P o m * scale)^T dO; the optional dS output carries the mask too.  All three
+ * product forms of the flag word; the packed short-sequence layout is not used. */
+int pk_attn_bwd_drop_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long long ldo, int o_bf16, const float* dO, long long lddo,
+                        const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
+                        float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long long work_floats,
+                        unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream);
 
 /* ---- the tokenizer's adversarial branch: cvivit.py:59-213 (Discriminator), :604-671 (hinge / gradient penalty / adaptive weight).
  * Images are CHANNELS-LAST pixel rows x[(b, y, x)][c] (f32, C % 4 == 0), so every nn.Conv2d (cvivit.py:115-127, 191) is pk_gemm on a patch matrix:

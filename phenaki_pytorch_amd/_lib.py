@@ -60,6 +60,7 @@ SIGNATURES = {
     'pk_q_attn_cached': [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P],
     'pk_attn_fwd': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P],
     'pk_attn_fwd_lse': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    'pk_attn_fwd_lse_drop': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _ULL, _ULL, _I, _F, _P],
     'pk_attn_small': [_P, _I, _P, _I, _P, _P, _F, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'pk_cfg_mix': [_P, _I, _I, _I, _I, _P, _I, _F, _I, _P, _I, _I, _I, _P],
     'pk_vocab_ntiles': [_I],
@@ -78,6 +79,9 @@ SIGNATURES = {
     'pk_layernorm_bwd': [_P, _LL, _P, _P, _LL, _P, _LL, _P, _LL, _P, _P, _F, _I, _I, _P],
     'pk_geglu': [_P, _LL, _I, _P, _LL, _I, _I, _P],
     'pk_geglu_bwd': [_P, _LL, _I, _P, _LL, _P, _LL, _I, _I, _P],
+    'pk_dropout_mask': [_ULL, _ULL, _I, _LL, _I, _P, _P],
+    'pk_geglu_drop': [_P, _LL, _I, _P, _LL, _I, _I, _ULL, _ULL, _I, _F, _P],
+    'pk_geglu_bwd_drop': [_P, _LL, _I, _P, _LL, _P, _LL, _I, _I, _ULL, _ULL, _I, _F, _P],
     'pk_leaky_bwd': [_P, _LL, _P, _LL, _P, _LL, _I, _I, _F, _P],
     'pk_scaled_diff': [_P, _P, _F, _P, _P, _LL, _P],
     'pk_sign': [_P, _F, _P, _LL, _P],
@@ -104,6 +108,7 @@ SIGNATURES = {
     'pk_attn_bwd': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'pk_attn_bwd_ws': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
     'pk_attn_bwd_work': [_I, _I, _I, _I, _I],
+    'pk_attn_bwd_drop_ws': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _ULL, _ULL, _I, _F, _P],
     'pk_im2col': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
     'pk_col2im': [_P, _LL, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     'pk_nchw_to_rows': [_P, _I, _I, _I, _I, _I, _P, _P],
@@ -457,7 +462,7 @@ def q_attn_cached(xq, wq, S, n, h, K, q_scale, scale, Kp, Vt, nk_pad, n_kv, nnul
 
 
 def attn_fwd(dtype, Qp, Kp, Vt, O, S, h, nq, n_kv, nnull, *, bias=None, kmask=None, slopes=None, causal=False, bias_table=None,
-             score_bound=None, lse=None):
+             score_bound=None, lse=None, drop=None):
     """bias: full (h, nq, n_kv) f32 tensor, or bias_table = (tab (h, L) f32, pos_code (n,) int32, offset, ...): the relative-position
     form.  score_bound: upper bound of sim + bias (python float) -> fixed-offset softmax; None: running-max flash loop.
     lse ((S h nq,) f32; the training forward): also write every row's log-sum-exp for pk_attn_bwd."""
@@ -467,6 +472,13 @@ def attn_fwd(dtype, Qp, Kp, Vt, O, S, h, nq, n_kv, nnull, *, bias=None, kmask=No
         bh, bld = bias.stride(0), bias.stride(1)
     else:
         bh, bld = 0, 0
+    if drop is not None:                                                  # attn_dropout > 0: a DropSite (seed, offset, thr, scale)
+        assert lse is not None and bias_table is None and score_bound is None
+        rc = load().pk_attn_fwd_lse_drop(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
+                                         1 if causal else 0, ptr(O), O.stride(-2), 1 if O.dtype == torch.float32 else 0, S, h, nq, n_kv, nnull, ptr(lse),
+                                         drop.seed, drop.offset, drop.thr, drop.scale, stream(O))
+        _check(rc, 'pk_attn_fwd_lse_drop')
+        return
     if lse is not None:
         assert bias_table is None and score_bound is None
         rc = load().pk_attn_fwd_lse(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
@@ -679,6 +691,53 @@ def geglu_bwd(h, goff, dout, dh, M, F):
     _check(rc, 'pk_geglu_bwd')
 
 
+def geglu_drop(h, goff, out, M, F, drop):
+    rc = load().pk_geglu_drop(ptr(h), h.stride(-2), goff, ptr(out), out.stride(-2), M, F, drop.seed, drop.offset, drop.thr, drop.scale, stream(h))
+    _check(rc, 'pk_geglu_drop')
+
+
+def geglu_bwd_drop(h, goff, dout, dh, M, F, drop):
+    rc = load().pk_geglu_bwd_drop(ptr(h), h.stride(-2), goff, ptr(dout), dout.stride(-2), ptr(dh), dh.stride(-2), M, F,
+                                  drop.seed, drop.offset, drop.thr, drop.scale, stream(h))
+    _check(rc, 'pk_geglu_bwd_drop')
+
+
+def dropout_mask(seed, offset, rows, cols, p, device):
+    """(rows, cols) uint8 on `device`, 1 = keep: the decisions the training kernels make for the site (seed, offset) at drop probability p
+    (dropout.keep_mask is the NumPy mirror)"""
+    from .dropout import quantize
+    out = torch.empty((rows, cols), device=device, dtype=torch.uint8)
+    rc = load().pk_dropout_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, quantize(p)[0], rows, cols, ptr(out), stream(out))
+    _check(rc, 'pk_dropout_mask')
+    return out
+
+
+class DropSite:
+    """one dropout site of a training step: the stream (seed, offset) read from the device's default torch generator on the host (no sync; the pattern
+    of TorchPhilox below) and the quantised probability (dropout.quantize: thr, p_eff, scale).  Taking a site advances the generator by 4 (its offset
+    granularity): the site's stream IS its offset, so layers, self- and cross-attention and the feed-forward never share a mask, and
+    torch.manual_seed(s) makes a step reproducible.  Held on the autograd ctx: the backward kernels regenerate the mask from it."""
+
+    def __init__(self, device, p):
+        from .dropout import quantize
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        gen = torch.cuda.default_generators[idx]
+        self.seed = gen.initial_seed() & 0xFFFFFFFFFFFFFFFF
+        self.offset = gen.get_offset()
+        gen.set_offset(self.offset + 4)
+        self.p = float(p)
+        self.thr, self.p_eff, self.scale = quantize(p)
+
+    @staticmethod
+    def of(module, device):
+        """the site of an nn.Dropout module, or None when it is inactive: like torch, dropout acts iff the module is in training mode and p > 0
+        (p below 2^-9 quantises to p_eff = 0: inactive)"""
+        if not module.training or module.p <= 0.:
+            return None
+        site = DropSite(device, module.p)
+        return site if site.thr > 0 else None
+
+
 def scaled_diff(a, b, scale, out, scale_dev=None):
     """out = (a - b) * scale (* scale_dev[0]) over contiguous f32 tensors of the same size"""
     rc = load().pk_scaled_diff(f32p(a, 'a'), f32p(b, 'b'), float(scale), ptr(scale_dev), ptr(out), a.numel(), stream(a))
@@ -777,7 +836,7 @@ def attn_train_prep_bwd(q, kv, null_kv, q_scale, k_scale, scale, dQh, dKh, dVh, 
 
 
 def attn_bwd(Qh, Kh, Vh, O, dO, dQh, dKh, dVh, S, h, n, n_kv, nnull, *, bias=None, kmask=None, dS=None, slopes=None, causal=False, split_bf16=False, lse=None,
-             bf16_products=False):
+             bf16_products=False, drop=None):
     """lse ((S h n,) f32 from attn_fwd(lse=...)): the backward skips its own log-sum-exp pass.  bf16_products: single bf16 MFMA products (the bf16 mode)"""
     dev = Qh.device
     flags = (1 if split_bf16 else 0) | (2 if lse is not None else 0) | (4 if bf16_products else 0)
@@ -786,6 +845,13 @@ def attn_bwd(Qh, Kh, Vh, O, dO, dQh, dKh, dVh, S, h, n, n_kv, nnull, *, bias=Non
     drow = torch.empty((S * h * n,), device=dev, dtype=torch.float32)
     nwork = load().pk_attn_bwd_work(S, h, n, n_kv, nnull)                  # few key tiles: partial dK / dV slabs of the query-tile groups
     work = torch.empty((nwork,), device=dev, dtype=torch.float32) if nwork > 0 else None
+    if drop is not None:                                                  # the forward's DropSite: the mask is regenerated
+        rc = load().pk_attn_bwd_drop_ws(ptr(Qh), ptr(Kh), ptr(Vh), ptr(O), O.stride(-2), 1 if O.dtype == torch.bfloat16 else 0, ptr(dO), dO.stride(-2), ptr(bias),
+                                        ptr(kmask), f32p(slopes, 'ALiBi slopes') if causal else None, 1 if causal else 0, ptr(dQh), ptr(dKh), ptr(dVh), ptr(dS),
+                                        ptr(lse), ptr(drow), S, h, n, n_kv, nnull, flags, ptr(work), nwork if nwork > 0 else 0,
+                                        drop.seed, drop.offset, drop.thr, drop.scale, stream(Qh))
+        _check(rc, 'pk_attn_bwd_drop_ws')
+        return
     rc = load().pk_attn_bwd_ws(ptr(Qh), ptr(Kh), ptr(Vh), ptr(O), O.stride(-2), 1 if O.dtype == torch.bfloat16 else 0, ptr(dO), dO.stride(-2), ptr(bias), ptr(kmask),
                                f32p(slopes, 'ALiBi slopes') if causal else None, 1 if causal else 0, ptr(dQh), ptr(dKh), ptr(dVh), ptr(dS), ptr(lse), ptr(drow), S, h, n, n_kv, nnull, flags,
                                ptr(work), nwork if nwork > 0 else 0, stream(Qh))

@@ -202,10 +202,13 @@ __device__ __forceinline__ void mask_vt_tail(Frag<float>& f, int kb, int g, int 
     }
 }
 
-template <typename T, int QF>
+// DROP (the training forward with attn_dropout > 0, attention.py:177): the softmax statistics (running max, row sum, lse) are those of the undropped
+// probabilities; the P that multiplies V is masked by the keep function (common.hpp) and the output scaled by 1 / (1 - p_eff).  A compile-time
+// flag: the DROP = false instantiation is the kernel as it was.
+template <typename T, int QF, bool DROP = false>
 // QF = 2 on f32 / split-bf16 operands (the training step's n = 576 forward, the f32 / bf16x3 parity modes): the compiler's free choice was
 // ~250 VGPRs + 32 AGPRs = one wave per SIMD, 256 resident workgroups for the 320 of a B = 8 call; two waves per SIMD put them in one round
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 && sizeof(T) != 2) ? 2 : 1))) void attn_fwd_kernel(const AttnArgs p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 && sizeof(T) != 2) ? 2 : 1))) void attn_fwd_kernel(const AttnArgs p, const DropParam<DROP> dr) {
     const int lane = threadIdx.x & 63, g = lane >> 4, lr = lane & 15;
     const int qtiles = p.nq_pad / (16 * QF);
     const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -246,6 +249,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
     int qrow[QF];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) { const int qi = q0 + qf * 16 + lr; qrow[qf] = qi < p.nq ? qi : p.nq - 1; }
+    uint32_t rowh[QF];                                                    // DROP: the hashed logical row (s h + hh) nq + i of the lane's query row(s)
+    if constexpr (DROP) {
+#pragma unroll
+        for (int qf = 0; qf < QF; ++qf) rowh[qf] = drop_row(dr, (uint32_t)sh * (uint32_t)p.nq + (uint32_t)(q0 + qf * 16 + lr));
+    }
     auto load_k = [&](Frag<T> (&fk)[2][2], int kb) {
 #pragma unroll
         for (int f = 0; f < 2; ++f)
@@ -336,6 +344,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
             m[qf] = mn;
 #pragma unroll
             for (int df = 0; df < 4; ++df) o[qf][df] *= alpha;
+            if constexpr (DROP) {
+                // the lane's keys kb + f * 16 + g * 4 + 0..3 are one group of the keep function: one draw per block f
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    const uint32_t w = drop_word(dr, rowh[qf], (uint32_t)(kb + f * 16 + g * 4) >> 2);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (!drop_keep(dr, w, r)) pr[qf][f * 4 + r] = 0.f;
+                }
+            }
         }
         Frag<T> fp[QF];
 #pragma unroll
@@ -360,7 +378,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
         float lt = l[qf];
         lt += __shfl_xor(lt, 16, 64);
         lt += __shfl_xor(lt, 32, 64);
-        const float inv = 1.0f / lt;
+        float inv = 1.0f / lt;
+        if constexpr (DROP) inv = dr.scale / lt;
         const int qi = q0 + qf * 16 + lr;
         if (qi < p.nq) {
 #pragma unroll
@@ -919,8 +938,9 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
                          const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                          const float* slopes, int causal, void* O, int ldo, int out_is_f32,
                          int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len, const int* pos_code,
-                         int code_off, int tab_run4, float score_bound, float* lse, void* stream) {
+                         int code_off, int tab_run4, float score_bound, float* lse, void* stream, const DropArgs* drop = nullptr) {
     if (!Qp || !Kp || !Vt || !O || S <= 0 || h <= 0) return PK_EINVAL;
+    if (drop && (!lse || bias_tab || (unsigned long long)S * h * nq > 0xFFFFFFFFull)) return PK_EINVAL;
     if (bias_tab && (bias || !pos_code || tab_len <= 0 || nnull != 0 || nq != n_kv || causal || kmask)) return PK_EINVAL;
     if (ldo & 3) return PK_EALIGN;
     int nq_pad, nk_pad;
@@ -938,7 +958,8 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
     const long waves = (long)S * h * (nq_pad / (16 * QF));
     dim3 grid((unsigned)((waves + 3) / 4)), block(256);
     static const int use_lds = [] { const char* e = getenv("PK_ATTN_LDS"); return e ? atoi(e) : 1; }();   // tuning knob
-    if (dtype == 1 && use_lds && (!lse || (!bias_tab && !(score_bound == score_bound))) && nnull + n_kv >= 64 && nq >= 64 &&
+    // drop (attn_dropout > 0): every shape goes to the LDS-free kernel below, the LDS-staged forms stay p = 0 only
+    if (!drop && dtype == 1 && use_lds && (!lse || (!bias_tab && !(score_bound == score_bound))) && nnull + n_kv >= 64 && nq >= 64 &&
         (size_t)S * h * nk_pad * 128 < 0xFFFFFFF0ull) {
         // measured on maskgit self-attention (S*h = 128, n = 576, bias): 16 query rows per wave + bias prefetch 41.2 us,
         // 32 rows per wave 44.5 us (its prefetch spills: 77 us); with a single key tile (n = 64) there is nothing to
@@ -985,7 +1006,7 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         PK_CHECK_LAUNCH();
         return PK_OK;
     }
-    if (dtype == 2 && use_lds && !lse && nnull + n_kv >= 64 && nq >= 128 && score_bound == score_bound && fabsf(score_bound) < 1e4f && !kmask && !causal && !bias &&
+    if (!drop && dtype == 2 && use_lds && !lse && nnull + n_kv >= 64 && nq >= 128 && score_bound == score_bound && fabsf(score_bound) < 1e4f && !kmask && !causal && !bias &&
         out_is_f32 && (size_t)S * h * nk_pad * 256 < 0xFFFFFFF0ull &&
         !((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) {
         // split-bf16 images, fixed-offset softmax (round 3): the same LDS-staged kernel on tiles twice as large (64 KB ring + the bias table:
@@ -1013,7 +1034,7 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         PK_CHECK_LAUNCH();
         return PK_OK;
     }
-    if (dtype == 2 && lse && use_lds && nnull == 0 && nq == n_kv && nq >= 128 && !kmask && !causal && out_is_f32 && !bias_tab &&
+    if (!drop && dtype == 2 && lse && use_lds && nnull == 0 && nq == n_kv && nq >= 128 && !kmask && !causal && out_is_f32 && !bias_tab &&
         (!bias || a.bias_vec) && (size_t)S * h * nk_pad * 256 < 0xFFFFFFF0ull &&
         !((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) {
         // training forward, split-bf16 (round 6): the LDS-staged kernel in its RUNNING-MAX form (the fixed-offset form needs a score bound on the
@@ -1042,17 +1063,33 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         }
     }
     if (bias_tab) return PK_EINVAL;                       // the table form exists in the LDS-staged kernel only
+    if (drop) {
+        if (dtype == 1) {
+            if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+            else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+            else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+        } else if (dtype == 0) {
+            if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+            else hipLaunchKernelGGL((attn_fwd_kernel<float, 1, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+        } else if (dtype == 2) {
+            if (!out_is_f32 || ((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) return PK_EINVAL;
+            if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+            else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1, true>), grid, block, 0, s, a, DropParam<true>(*drop));
+        } else return PK_EINVAL;
+        PK_CHECK_LAUNCH();
+        return PK_OK;
+    }
     if (dtype == 1) {
-        if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4>), grid, block, 0, s, a);
-        else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1>), grid, block, 0, s, a);
+        if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4>), grid, block, 0, s, a, DropParam<false>{});
+        else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2>), grid, block, 0, s, a, DropParam<false>{});
+        else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1>), grid, block, 0, s, a, DropParam<false>{});
     } else if (dtype == 0) {
-        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attn_fwd_kernel<float, 1>), grid, block, 0, s, a);
+        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2>), grid, block, 0, s, a, DropParam<false>{});
+        else hipLaunchKernelGGL((attn_fwd_kernel<float, 1>), grid, block, 0, s, a, DropParam<false>{});
     } else if (dtype == 2) {
         if (!out_is_f32 || ((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) return PK_EINVAL;
-        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1>), grid, block, 0, s, a);
+        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2>), grid, block, 0, s, a, DropParam<false>{});
+        else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1>), grid, block, 0, s, a, DropParam<false>{});
     } else return PK_EINVAL;
     PK_CHECK_LAUNCH();
     return PK_OK;
@@ -1077,6 +1114,21 @@ extern "C" int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const 
     if (!lse) return PK_EINVAL;
     return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
                          nullptr, 0, 0, __builtin_nanf(""), lse, stream);
+}
+
+// pk_attn_fwd_lse with attn_dropout (attention.py:177: dropout on the probabilities between the softmax and attn @ v): lse is that of the undropped
+// scores; element (row (s h + hh) nq + i, column j over the nnull + n_kv keys) of the probabilities is kept iff the keep function of stream
+// (seed, offset) says so (keep_thr in [1, 256]: dropped iff its 8-bit draw < keep_thr) and O is scaled by `scale` = 1 / (1 - keep_thr / 256).
+// Every shape runs on the LDS-free kernel.
+extern "C" int pk_attn_fwd_lse_drop(int dtype, const void* Qp, const void* Kp, const void* Vt,
+                                    const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
+                                    const float* slopes, int causal, void* O, int ldo, int out_is_f32,
+                                    int S, int h, int nq, int n_kv, int nnull, float* lse,
+                                    unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream) {
+    if (!lse || keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
+    const DropArgs d = drop_keys(seed, offset, keep_thr, scale);
+    return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
+                         nullptr, 0, 0, __builtin_nanf(""), lse, stream, &d);
 }
 
 // attention.py:128-182 for short self-attention sequences (n <= 64, no null keys) straight from the projection outputs:

@@ -330,8 +330,12 @@ __device__ __forceinline__ bool score(const AttnBwdArgs& p, int s, int h, int gi
 // SIMD -- 256 resident workgroups, so the 576 of a B = 8 step ran in three rounds
 // (round 6, measured and removed: a variant whose dS rows shared the V tile's LDS -- 52 KB and a 168-register cap, three workgroups per CU so that the 576
 // workgroups of a B = 8 step run in one round instead of 512 + 64 -- spilled 210 VGPRs and lost: training step 30.13 vs 29.34 ms same-box.)
-template <int X3>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_q_kernel(const AttnBwdArgs p) {
+// DROP (attn_dropout > 0, attention.py:177; never with the packed layout): dP = (dO V^T) o m / (1 - p_eff) with m from the keep function (common.hpp) at
+// the logical element (row sh n + gi, column j); dS = P o (dP - D) as before (O, hence D, was formed from the dropped P), so the dS output carries the
+// mask too.  A lane holds 4 query rows of ONE key here -- the transpose of a keep-function group -- so lane b of a quad draws the word of (row b of the
+// lane group's four, the quad's 4 keys) and the quad exchanges them: one draw per lane per 16 x 16 block.
+template <int X3, bool DROP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_q_kernel(const AttnBwdArgs p, const DropParam<DROP> dr) {
     typedef typename OpFragOf<X3>::type OF;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Ks = sm; float* Vs = sm + TSZ; float* Kt = sm + 2 * TSZ; float* Ps = sm + 3 * TSZ;
@@ -429,6 +433,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     }
     // ---- pass 2: dS and dQ^
+    uint32_t rowh = 0;                                             // DROP: hashed logical row of query row kq * 4 + (r & 3) of this wave's 16
+    if constexpr (DROP) rowh = drop_row(dr, (uint32_t)sh * (uint32_t)p.n + (uint32_t)(i0 + m0 + kq * 4 + (r & 3)));
     f32x4 accQ[4] = PK_ZERO4;
     fetch_tile<64>(kreg, Kbase, 64, 0, klive);
     fetch_tile<64>(vreg, Vbase, 64, 0, klive);
@@ -446,14 +452,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         mma_regA<4, 2, OF>(fqx, Ks, TLD, accS, lane);
         mma_regA<4, 2, OF>(fdox, Vs, TLD, accP, lane);
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
+        for (int nb = 0; nb < 4; ++nb) {
+            uint32_t wq = 0;
+            if constexpr (DROP) wq = drop_word(dr, rowh, (uint32_t)(kt * 64 + nb * 16 + (r & ~3)) >> 2);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int gi = i0 + m0 + kq * 4 + i, j = kt * 64 + nb * 16 + r;
+                float dp = accP[nb][i];
+                if constexpr (DROP) {
+                    const uint32_t w = (uint32_t)__shfl((int)wq, i, 4);       // the word of row kq * 4 + i, drawn by lane i of the quad; this lane's key is byte r & 3
+                    dp = drop_keep(dr, w, r & 3) ? dp * dr.scale : 0.f;
+                }
                 float sc, ds = 0.f;
-                if (score(p, s, h, gi, j, accS[nb][i], sc)) ds = __expf(sc - lse[i]) * (accP[nb][i] - Dl[i]);
+                if (score(p, s, h, gi, j, accS[nb][i], sc)) ds = __expf(sc - lse[i]) * (dp - Dl[i]);
                 Ps[(m0 + kq * 4 + i) * TLD + nb * 16 + r] = ds;
             }
+        }
         if (p.dS) {
             // the score gradient leaves through the wave's own LDS rows (round 6): 16 lanes x 16 bytes = one whole 256-byte row segment per store
             // instead of 16 four-byte stores per lane in the accumulator layout (85 MB per layer at n = 576: kernel Q 190 vs 115 us without dS)
@@ -488,8 +502,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // LDS holds q^ [32][68], dO [32][68] (B operands of the TRANSPOSED scores S^T[j][i], dP^T[j][i]), their transposes [64][36] (B operands of
 // dV = P^T dO, dK^ = dS^T q^) and one wave-private [64][36] buffer that carries P^T and then dS^T (46 KB: three workgroups per CU).
 constexpr int QT = 32, TLQ = 36;
-template <int X3>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_bwd_kv_kernel(const AttnBwdArgs p) {
+// DROP: dV = (P o m / (1 - p_eff))^T dO and dS^T from the masked, scaled dP^T.  A lane holds 4 consecutive keys of one query row: one keep-function group.
+template <int X3, bool DROP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_bwd_kv_kernel(const AttnBwdArgs p, const DropParam<DROP> dr) {
     typedef typename OpFragOf<X3>::type OF;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Qs = sm; float* dOs = sm + QT * TLD; float* Qt = sm + 2 * QT * TLD; float* dOt = Qt + 64 * TLQ; float* PS = dOt + 64 * TLQ;
@@ -540,13 +555,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int nb = 0; nb < 2; ++nb) {
             const int ci = nb * 16 + r, gi = i0 + ci;
             const float lse = lse_s[ci], Dr = D_s[ci];
+            uint32_t w = 0;
+            if constexpr (DROP) w = drop_word(dr, drop_row(dr, (uint32_t)sh * (uint32_t)p.n + (uint32_t)gi), (uint32_t)(j0 + m0 + kq * 4) >> 2);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float sc;
                 pr[nb][i] = 0.f;
                 if (score(p, s, h, gi, j0 + m0 + kq * 4 + i, accS[nb][i], sc)) pr[nb][i] = __expf(sc - lse);
-                dsv[nb][i] = pr[nb][i] * (accP[nb][i] - Dr);
-                PS[(m0 + kq * 4 + i) * TLQ + ci] = pr[nb][i];
+                if constexpr (DROP) {
+                    const float ms = drop_keep(dr, w, i) ? dr.scale : 0.f;
+                    dsv[nb][i] = pr[nb][i] * (accP[nb][i] * ms - Dr);
+                    PS[(m0 + kq * 4 + i) * TLQ + ci] = pr[nb][i] * ms;
+                } else {
+                    dsv[nb][i] = pr[nb][i] * (accP[nb][i] - Dr);
+                    PS[(m0 + kq * 4 + i) * TLQ + ci] = pr[nb][i];
+                }
             }
         }
         // dV[j][d] += sum_i P^T[j][i] dO^T[d][i]   (A rows = this wave's own 16 rows of PS: program order is enough)
@@ -649,12 +672,14 @@ extern "C" int pk_attn_bwd(const float* Qh, const float* Kh, const float* Vh, co
                           nullptr, 0, stream);
 }
 // work (pk_attn_bwd_work floats, or NULL): lets kernel KV deal the query tiles of a key tile to several workgroups when there are few key tiles
-extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
-                              const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                              float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats, void* stream) {
+static int attn_bwd_impl(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
+                         const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
+                         float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats, void* stream,
+                         const DropArgs* drop) {
     if (!Qh || !Kh || !Vh || !O || !dO || !dQh || !dKh || !dVh || !lse || !Drow || S <= 0 || heads <= 0 || n <= 0 || n_kv <= 0 || nnull < 0) return PK_EINVAL;
     if (!al16(Qh) || !al16(Kh) || !al16(Vh) || !al16(dO) || (lddo & 3) || !al16(O) || (ldo & (o_bf16 ? 7 : 3))) return PK_EALIGN;
     if ((long)S * heads > 0x7fffffffL / 64) return PK_EINVAL;
+    if (drop && (unsigned long long)S * heads * n > 0xFFFFFFFFull) return PK_EINVAL;
     if (causal && (!slopes || n != n_kv)) return PK_EINVAL;
     const int have_lse = (split_bf16 >> 1) & 1;                         // flags: bit 0 split-bf16 tile products, bit 1 lse (S heads, n) given by pk_attn_fwd_lse,
     const bool bf16_products = (split_bf16 >> 2) & 1;                   // bit 2: single bf16 products (the bf16 compute mode)
@@ -662,7 +687,7 @@ extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh,
     AttnBwdArgs p{Qh, Kh, Vh, O, ldo, o_bf16, dO, lddo, bias, kmask, slopes, causal, dQh, dKh, dVh, dS, lse, Drow, S, heads, n, nnull + n_kv, nnull, 0, 0, heads, S * heads, 0, have_lse};
     static const bool pack_on = !(getenv("PK_ATTN_BWD_PACK") && getenv("PK_ATTN_BWD_PACK")[0] == '0');      // A/B switch
     // (the packed layout re-indexes the rows: lse is laid out [S heads][n], the flat index of a packed row is the same (S h n contiguous) -> usable as is)
-    if (pack_on && nnull == 0 && n == n_kv && n <= 32 && !dS) {
+    if (pack_on && !drop && nnull == 0 && n == n_kv && n <= 32 && !dS) {             // (the packed layout re-indexes the rows: p = 0 only)
         // short self-attention (the C-ViViT temporal transformers: n = 9 at 512 sequences x 8 heads): 64 / n whole (sequence, head) groups per tile
         // instead of one -- the flat [S*h][n][64] arrays are the same memory either way
         p.pack_n = n;
@@ -683,6 +708,16 @@ extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh,
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
         attr_done = true;
     }
+    static bool attr_drop_done = false;
+    if (drop && !attr_drop_done) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
+        attr_drop_done = true;
+    }
     const int nqt = (p.n + 63) / 64, nktt = (p.nkt + 63) / 64;
     if (work && !p.pack_n) {
         int chunk;
@@ -694,15 +729,26 @@ extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh,
     }
     const dim3 gq((unsigned)((long)p.S * p.heads * nqt)), gk((unsigned)((long)p.S * p.heads * nktt * (p.kv_split > 1 ? p.kv_split : 1)));
     static const bool split_on = !(getenv("PK_ATTN_BWD_SPLIT") && getenv("PK_ATTN_BWD_SPLIT")[0] == '0');     // A/B switch
-    if (bf16_products) {
-        hipLaunchKernelGGL(attn_bwd_q_kernel<2>, gq, dim3(256), 4 * TSZ * 4, s, p);
-        hipLaunchKernelGGL(attn_bwd_kv_kernel<2>, gk, dim3(256), KV_SMEM, s, p);
+    if (drop) {
+        if (bf16_products) {
+            hipLaunchKernelGGL((attn_bwd_q_kernel<2, true>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<true>(*drop));
+            hipLaunchKernelGGL((attn_bwd_kv_kernel<2, true>), gk, dim3(256), KV_SMEM, s, p, DropParam<true>(*drop));
+        } else if (split_bf16 && split_on) {
+            hipLaunchKernelGGL((attn_bwd_q_kernel<1, true>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<true>(*drop));
+            hipLaunchKernelGGL((attn_bwd_kv_kernel<1, true>), gk, dim3(256), KV_SMEM, s, p, DropParam<true>(*drop));
+        } else {
+            hipLaunchKernelGGL((attn_bwd_q_kernel<0, true>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<true>(*drop));
+            hipLaunchKernelGGL((attn_bwd_kv_kernel<0, true>), gk, dim3(256), KV_SMEM, s, p, DropParam<true>(*drop));
+        }
+    } else if (bf16_products) {
+        hipLaunchKernelGGL((attn_bwd_q_kernel<2>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<false>{});
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<2>), gk, dim3(256), KV_SMEM, s, p, DropParam<false>{});
     } else if (split_bf16 && split_on) {
-        hipLaunchKernelGGL(attn_bwd_q_kernel<1>, gq, dim3(256), 4 * TSZ * 4, s, p);
-        hipLaunchKernelGGL(attn_bwd_kv_kernel<1>, gk, dim3(256), KV_SMEM, s, p);
+        hipLaunchKernelGGL((attn_bwd_q_kernel<1>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<false>{});
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<1>), gk, dim3(256), KV_SMEM, s, p, DropParam<false>{});
     } else {
-        hipLaunchKernelGGL(attn_bwd_q_kernel<0>, gq, dim3(256), 4 * TSZ * 4, s, p);
-        hipLaunchKernelGGL(attn_bwd_kv_kernel<0>, gk, dim3(256), KV_SMEM, s, p);
+        hipLaunchKernelGGL((attn_bwd_q_kernel<0>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<false>{});
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<0>), gk, dim3(256), KV_SMEM, s, p, DropParam<false>{});
     }
     PK_CHECK_LAUNCH();
     if (p.kv_split > 1) {                                                // dK^ / dV = the slabs added in index order (one launch for both)
@@ -711,4 +757,21 @@ extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh,
         return pk_sum_batch_multi(jobs, 2, stream);
     }
     return PK_OK;
+}
+extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
+                              const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
+                              float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats, void* stream) {
+    return attn_bwd_impl(Qh, Kh, Vh, O, ldo, o_bf16, dO, lddo, bias, kmask, slopes, causal, dQh, dKh, dVh, dS, lse, Drow, S, heads, n, n_kv, nnull, split_bf16,
+                         work, work_floats, stream, nullptr);
+}
+// pk_attn_bwd_ws for a forward that ran pk_attn_fwd_lse_drop with the same (seed, offset, keep_thr, scale): the mask is regenerated, never stored.
+// O is the forward's (dropped) output; the optional dS carries the mask too.  The packed short-sequence layout is not used.
+extern "C" int pk_attn_bwd_drop_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
+                                   const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
+                                   float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats,
+                                   unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream) {
+    if (keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
+    const DropArgs d = drop_keys(seed, offset, keep_thr, scale);
+    return attn_bwd_impl(Qh, Kh, Vh, O, ldo, o_bf16, dO, lddo, bias, kmask, slopes, causal, dQh, dKh, dVh, dS, lse, Drow, S, heads, n, n_kv, nnull, split_bf16,
+                         work, work_floats, stream, &d);
 }

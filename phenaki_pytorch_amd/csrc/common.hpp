@@ -255,6 +255,33 @@ __device__ __host__ __forceinline__ void uniform24x4(uint32_t seed_lo, uint32_t 
     u[3] = (float)(((w0 & 0xFFu) << 16) | ((w1 & 0xFFu) << 8) | (w2 & 0xFFu)) * k;
 }
 
+// ---- dropout keep decisions of the training kernels (reference attention.py:45-52 ff_dropout, :177 attn_dropout) ------------------------------
+// keep(seed, offset, row, col) is a pure function of the site's stream (seed, offset) and of the two factors of the logical element index
+// row * cols + col -- attention: row = (s heads + h) n + i, col = j over the nnull + n_kv keys (null keys first); feed-forward: row = token row,
+// col over the true inner width F -- so the forward kernel, both attention backward kernels and pk_dropout_mask agree whatever their tiling.
+// The generator is the counter hash above, not philox4x32_10: ONE 32-bit word (two v_mul_lo_u32 once the row's hash is hoisted) serves the 4
+// consecutive columns of group col >> 2 with 8 bits each, and that group is exactly what a lane of the forward kernel and of the backward kernel
+// that forms S^T holds (4 consecutive keys of one query row); the kernel that holds the transpose lets each lane of a quad draw ONE word and
+// exchanges them inside the quad.  A Philox call is 10 rounds of 4 multiplies for 128 bits = a 4 x 4 block, which no lane of any of the three
+// layouts owns: every lane would redo the block's draw for its own 4 elements.  keep iff byte >= thr, thr = round(256 p) (host:
+// dropout.py quantize -> p_eff = thr / 256, survivors scaled by 1 / (1 - p_eff)).  phenaki_pytorch_amd/dropout.py mirrors this in NumPy.
+struct DropArgs { uint32_t k0, k1, thr; float scale; };
+__device__ __host__ __forceinline__ DropArgs drop_keys(uint64_t seed, uint64_t offset, int thr, float scale) {
+    DropArgs d;
+    d.k0 = mix32((uint32_t)seed ^ mix32((uint32_t)offset + 0x9e3779b9u));
+    d.k1 = mix32((uint32_t)(seed >> 32) + 0x85ebca6bu * ((uint32_t)(offset >> 32) + 1u) + d.k0);
+    d.thr = (uint32_t)thr;
+    d.scale = scale;
+    return d;
+}
+// the last parameter of a kernel with a compile-time DROP flag: nothing at DROP = false (that instantiation is the kernel without dropout), DropArgs at true
+template <bool DROP> struct DropParam {};
+template <> struct DropParam<true> : DropArgs { DropParam(const DropArgs& d) : DropArgs(d) {} };
+__device__ __host__ __forceinline__ uint32_t drop_row(const DropArgs& d, uint32_t row) { return mix32(row ^ d.k0); }
+// the draws of columns 4 grp .. 4 grp + 3 of the row whose drop_row() is rowh: byte e belongs to column 4 grp + e
+__device__ __host__ __forceinline__ uint32_t drop_word(const DropArgs& d, uint32_t rowh, uint32_t grp) { return mix32(rowh + 0x9e3779b9u * grp + d.k1); }
+__device__ __host__ __forceinline__ bool drop_keep(const DropArgs& d, uint32_t word, int e) { return ((word >> (8 * e)) & 255u) >= d.thr; }
+
 // ---- torch's device RNG, reproduced (SURVEY.md 7 "phase 2"; reference phenaki_pytorch.py:69-70, :88-93: noise = zeros_like(t).uniform_(0, 1)) ----
 // torch.Tensor.uniform_ on a HIP device fills element li of a tensor of `numel` elements from Philox4x32-10 (rocRAND) as follows
 // (ATen/native/cuda/DistributionTemplates.h: distribution_elementwise_grid_stride_kernel, block 256, unroll 4):

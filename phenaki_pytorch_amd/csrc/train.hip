@@ -326,6 +326,54 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const float* __restrict_
     }
 }
 
+// ---- the same with ff_dropout (attention.py:45-52: Dropout behind GEGLU): out = geglu(h) o m / (1 - p_eff) in the same pass; backward: dout is masked
+// and scaled before the GEGLU derivative.  m = the keep function (common.hpp) at (row, column) -- a thread's 4 columns are one of its groups -- and is
+// regenerated, never stored.  Columns >= F (the pad up to the stored width) are written as zeros.
+__global__ __launch_bounds__(256) void geglu_drop_kernel(const float* __restrict__ h, long ldh, int goff, float* __restrict__ out, long ldo, int M, int F4, long total,
+                                                         const DropArgs dr) {
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = (int)(idx % F4) * 4;
+        const long r = idx / F4;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(h + r * ldh + c), gv = *reinterpret_cast<const f32x4*>(h + r * ldh + goff + c);
+        const uint32_t w = drop_word(dr, drop_row(dr, (uint32_t)r), (uint32_t)c >> 2);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = drop_keep(dr, w, j) ? xv[j] * gelu_erf(gv[j]) * dr.scale : 0.f;
+        *reinterpret_cast<f32x4*>(out + r * ldo + c) = o;
+    }
+}
+__global__ __launch_bounds__(256) void geglu_bwd_drop_kernel(const float* __restrict__ h, long ldh, int goff, const float* __restrict__ dout, long ldd,
+                                                             float* __restrict__ dh, long lddh, int M, int F4, long total, const DropArgs dr) {
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = (int)(idx % F4) * 4;
+        const long r = idx / F4;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(h + r * ldh + c), gv = *reinterpret_cast<const f32x4*>(h + r * ldh + goff + c);
+        const f32x4 dv = *reinterpret_cast<const f32x4*>(dout + r * ldd + c);
+        const uint32_t w = drop_word(dr, drop_row(dr, (uint32_t)r), (uint32_t)c >> 2);
+        f32x4 dxv, dgv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d = drop_keep(dr, w, j) ? dv[j] * dr.scale : 0.f;
+            dxv[j] = d * gelu_erf(gv[j]);
+            dgv[j] = d * xv[j] * gelu_grad(gv[j]);
+        }
+        *reinterpret_cast<f32x4*>(dh + r * lddh + c) = dxv;
+        *reinterpret_cast<f32x4*>(dh + r * lddh + goff + c) = dgv;
+    }
+}
+// keep decisions of the logical index range [0, rows) x [0, cols) as bytes (1 = keep): what the kernels above and the attention kernels apply (tests, debugging)
+__global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char* __restrict__ out, long rows, int cols, long total, const DropArgs dr) {
+    const int G = (cols + 3) >> 2;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int g = (int)(idx % G);
+        const long r = idx / G;
+        const uint32_t w = drop_word(dr, drop_row(dr, (uint32_t)r), (uint32_t)g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (g * 4 + j < cols) out[r * cols + g * 4 + j] = drop_keep(dr, w, j) ? 1 : 0;
+    }
+}
+
 // ---- LeakyReLU backward from the activation's OUTPUT (the position-bias MLP, attention.py:243-247: sign(y) == sign(pre-activation)) ---
 __global__ __launch_bounds__(256) void leaky_bwd_kernel(const float* __restrict__ y, long ldy, const float* __restrict__ dy, long lddy,
                                                         float* __restrict__ dz, long lddz, int N, float slope, long total) {
@@ -811,6 +859,35 @@ extern "C" int pk_geglu_bwd(const float* h, long ldh, int goff, const float* dou
     if ((F & 3) || (goff & 3) || (ldh & 3) || (ldd & 3) || (lddh & 3) || !al16(h) || !al16(dout) || !al16(dh)) return PK_EALIGN;
     const long total = (long)M * (F >> 2);
     hipLaunchKernelGGL(geglu_bwd_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, dout, ldd, dh, lddh, M, F >> 2, total);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+// pk_geglu / pk_geglu_bwd with ff_dropout: stream (seed, offset), keep_thr in [1, 256] (dropped iff the 8-bit draw < keep_thr), scale = 1 / (1 - keep_thr / 256)
+extern "C" int pk_geglu_drop(const float* h, long ldh, int goff, float* out, long ldo, int M, int F, unsigned long long seed, unsigned long long offset,
+                             int keep_thr, float scale, void* stream) {
+    if (!h || !out || M <= 0 || F <= 0 || goff < F || keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
+    if ((F & 3) || (goff & 3) || (ldh & 3) || (ldo & 3) || !al16(h) || !al16(out)) return PK_EALIGN;
+    const long total = (long)M * (F >> 2);
+    hipLaunchKernelGGL(geglu_drop_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, out, ldo, M, F >> 2, total, drop_keys(seed, offset, keep_thr, scale));
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+extern "C" int pk_geglu_bwd_drop(const float* h, long ldh, int goff, const float* dout, long ldd, float* dh, long lddh, int M, int F, unsigned long long seed,
+                                 unsigned long long offset, int keep_thr, float scale, void* stream) {
+    if (!h || !dout || !dh || M <= 0 || F <= 0 || goff < F || keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
+    if ((F & 3) || (goff & 3) || (ldh & 3) || (ldd & 3) || (lddh & 3) || !al16(h) || !al16(dout) || !al16(dh)) return PK_EALIGN;
+    const long total = (long)M * (F >> 2);
+    hipLaunchKernelGGL(geglu_bwd_drop_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, dout, ldd, dh, lddh, M, F >> 2, total,
+                       drop_keys(seed, offset, keep_thr, scale));
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+// out (rows, cols) bytes, 1 = keep: the keep function of stream (seed, offset) at threshold keep_thr in [0, 256] over the logical index range
+extern "C" int pk_dropout_mask(unsigned long long seed, unsigned long long offset, int keep_thr, long rows, int cols, unsigned char* out, void* stream) {
+    if (!out || rows <= 0 || cols <= 0 || rows > 0xFFFFFFFFL || keep_thr < 0 || keep_thr > 256) return PK_EINVAL;
+    const long total = rows * ((cols + 3) >> 2);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), out, rows, cols, total, drop_keys(seed, offset, keep_thr, 1.0f));
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

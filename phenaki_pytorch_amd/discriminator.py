@@ -425,6 +425,9 @@ def _attention_second_order(attn, x, S, n, dt):
     """attn(x) + x (cvivit.py:166-168; attention.py:132-182 with num_null_kv = 0, no mask / bias) as a graph of Functions that can be differentiated
     twice: LayerNorm, l2norm x scale and softmax carry their own second derivatives (pk_row_*), the five products are _MM / _Affine"""
     assert attn.num_null_kv == 0 and not attn.causal
+    if attn.attn_dropout.training and attn.attn_dropout.p > 0.:
+        raise NotImplementedError('the twice-differentiable attention of the gradient penalty has no dropout (the reference builds the discriminator\'s '
+                                  'attention without a dropout argument, cvivit.py:166-168): build it with dropout = 0 or call .eval() on attn_dropout')
     h = attn.heads
     xn = _GammaLayerNorm.apply(x, attn.norm.gamma, attn.norm.beta, attn.norm.eps)
     q = mm(xn, attn.to_q.weight, False, True, dt)

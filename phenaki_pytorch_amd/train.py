@@ -11,7 +11,7 @@ Every block of the trunk is ONE torch.autograd.Function whose forward and backwa
     _AttnBlock      x + to_out(attention(norm(x) [, context]))                 pk_layernorm, pk_gemm, pk_attn_prep, pk_attn_fwd
                                                                                / pk_attn_train_prep, pk_attn_bwd, pk_attn_train_prep_bwd,
                                                                                  pk_pack + pk_gemm (dX, dW), pk_layernorm_bwd
-    _FFBlock        x + W2 geglu(W1 LayerNorm(x))                              pk_layernorm, pk_gemm, pk_geglu / pk_geglu_bwd, ...
+    _FFBlock        x + W2 dropout(geglu(W1 LayerNorm(x)))                     pk_layernorm, pk_gemm, pk_geglu[_drop] / pk_geglu_bwd[_drop], ...
     _LayerNormFn    norm_out                                                   pk_layernorm        / pk_layernorm_bwd
     _PositionBias   ContinuousPositionBias as (heads, n, n)                    relative-position-table MLP + pk_bias_gather / pk_bias_scatter
     _VocabCrossEntropy   to_logits + cross entropy on the masked rows          pk_vocab_sample, pk_vocab_ce / pk_ce_grad_slab + pk_gemm
@@ -24,7 +24,11 @@ Round 6 (launch count): the W / W^T images of a whole Transformer are persistent
 pk_pack_table); the activation transposes of a backward block leave in one launch (`transposes`, pk_pack_multi), its K-slice sums and column sums
 in another (L.reduce_multi); the forward attention hands its log-sum-exp to the backward kernels (pk_attn_fwd_lse); the critic's gumbel sample and
 the cross entropy share one pass over the vocabulary (`_VocabCrossEntropy(shared=...)`).
-Limits (asserted): dropout 0 (the reference default).  The tokenizer's own reconstruction step is train_cvivit.py.
+Dropout (attn_dropout / ff_dropout of the reference's constructors, attention.py:45-52, :177): active iff the nn.Dropout module is in training
+mode and p > 0, as in torch; the masks are made inside the kernels (pk_attn_fwd_lse_drop / pk_attn_bwd_drop_ws, pk_geglu_drop / pk_geglu_bwd_drop)
+from a (seed, offset) stream read off the device's default torch generator on the host -- one `L.DropSite` per dropout site per call, kept on the
+autograd ctx so that the backward kernels regenerate the mask (nothing is stored).  Inactive dropout makes exactly the calls of a p = 0 module.
+The tokenizer's own reconstruction step is train_cvivit.py.
 """
 import math
 import os
@@ -317,7 +321,7 @@ class _FFBlock(torch.autograd.Function):
         return img
 
     @staticmethod
-    def forward(ctx, x, ln_w, ln_b, w1, w2, dtype, eps, img):
+    def forward(ctx, x, ln_w, ln_b, w1, w2, dtype, eps, img, drop=None):
         M, D = x.shape
         F = w2.shape[1]
         Fp = round_up(F, 8)
@@ -331,11 +335,14 @@ class _FFBlock(torch.autograd.Function):
         h = _f32((M, 2 * Fp), dev)
         L.gemm(dtype, xa if xa is not None else xn, img['w1p'], M, 2 * Fp, D, C=h)
         a = _f32((M, Fp), dev)
-        L.geglu(h, Fp, a, M, Fp)
+        if drop is None:
+            L.geglu(h, Fp, a, M, Fp)
+        else:                                                            # ff_dropout: a = geglu(h) o m / (1 - p_eff); the dropped a is the operand of dW2
+            L.geglu_drop(h, Fp, a, M, Fp, drop)
         y = _f32((M, D), dev)
         L.gemm(dtype, a_operand(dtype, a), img['w2'], M, D, Fp, C=y, res=x)
         ctx.save_for_backward(x, ln_w, w1, w2, xn, h, a)
-        ctx.dtype, ctx.eps, ctx.Fp, ctx.img = dtype, eps, Fp, img
+        ctx.dtype, ctx.eps, ctx.Fp, ctx.img, ctx.drop = dtype, eps, Fp, img, drop
         return y
 
     @staticmethod
@@ -362,7 +369,10 @@ class _FFBlock(torch.autograd.Function):
             _weight_grad_gemm(dtype, dyT, aT, D, F, Mp, dW2, sums)
         # ---- GEGLU
         dh = _f32((M, 2 * Fp), dev)
-        L.geglu_bwd(h, Fp, da, dh, M, Fp)
+        if ctx.drop is None:
+            L.geglu_bwd(h, Fp, da, dh, M, Fp)
+        else:                                                            # da o m / (1 - p_eff) in front of the GEGLU derivative (the mask is regenerated)
+            L.geglu_bwd_drop(h, Fp, da, dh, M, Fp, ctx.drop)
         # ---- first Linear: dxn = dh W1 (the padded layout, transposed), dW1 = dh^T xn in two row groups (value | gate)
         dhT, xnT, dhA = transposes(dtype, [(dh, 'a'), (xn, 'w')], [dh])   # (2 Fp, Mp), (D, Mp)
         dxn = _f32((M, D), dev)
@@ -377,7 +387,7 @@ class _FFBlock(torch.autograd.Function):
         L.reduce_multi(sums, cs)
         if dW2p is not None:
             dW2 = dW2p[:, :F].contiguous()
-        return dx, dg, db, dW1, dW2, None, None, None
+        return dx, dg, db, dW1, dW2, None, None, None, None
 
 
 class _PEGBlock(torch.autograd.Function):
@@ -415,7 +425,7 @@ class _AttnBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, context, gamma, beta, cgamma, cbeta, wq, wkv, null_kv, q_scale, k_scale, wo, bias, kmask, meta):
-        dtype, S, n, n_ctx, heads, scale, eps, slopes, img = meta
+        dtype, S, n, n_ctx, heads, scale, eps, slopes, drop, img = meta
         if img is None:                                                  # a direct caller (no WeightImages of the whole Transformer): pack here
             wi = WeightImages(dtype, x.device)
             img = dict(wq=wi.both(wq), wkv=wi.both(wkv), wo=wi.both(wo))
@@ -454,7 +464,11 @@ class _AttnBlock(torch.autograd.Function):
         # forward's scores are products of bf16 operands, so the hand-over needs the backward's single-bf16-product form (ATTN_BWD_BF16); with the
         # split-bf16 backward (PK_ATTN_BWD_BF16=0) that mode keeps the extra pass
         lse = _f32((S * heads * n,), dev) if (dtype != L.BF16 or ATTN_BWD_BF16) else None
-        L.attn_fwd(dtype, Qp, Kp, Vt, o, S, heads, n, n_kv, nnull, bias=bias, kmask=kmask, slopes=slopes, causal=slopes is not None, lse=lse)
+        if drop is not None and lse is None:                             # the dropout forward always hands its log-sum-exp over (scratch for the split-bf16 backward of the bf16 mode)
+            lse = _f32((S * heads * n,), dev)
+        L.attn_fwd(dtype, Qp, Kp, Vt, o, S, heads, n, n_kv, nnull, bias=bias, kmask=kmask, slopes=slopes, causal=slopes is not None, lse=lse, drop=drop)
+        if dtype == L.BF16 and not ATTN_BWD_BF16:
+            lse = None
         y = _f32((M, D), dev)
         L.gemm(dtype, a_operand(dtype, o), img['wo'][0], M, D, inner, C=y, res=x)
         ctx.save_for_backward(x, context, gamma, cgamma, wq, wkv, null_kv, q_scale, k_scale, wo, bias, kmask, xn, src, q, kv, o, lse)
@@ -464,7 +478,7 @@ class _AttnBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, context, gamma, cgamma, wq, wkv, null_kv, q_scale, k_scale, wo, bias, kmask, xn, src, q, kv, o, lse = ctx.saved_tensors
-        dtype, S, n, n_ctx, heads, scale, eps, slopes, img = ctx.meta
+        dtype, S, n, n_ctx, heads, scale, eps, slopes, drop, img = ctx.meta
         dev = x.device
         M, D = x.shape
         inner = wq.shape[0]
@@ -484,7 +498,7 @@ class _AttnBlock(torch.autograd.Function):
         want_dbias = bias is not None and ctx.needs_input_grad[12]
         dS = _f32((S, heads * n * n_kv), dev) if want_dbias else None
         L.attn_bwd(Qh, Kh, Vh, o, do, dQh, dKh, dVh, S, heads, n, n_kv, nnull, bias=bias, kmask=kmask, dS=dS, slopes=slopes, causal=slopes is not None,
-                   split_bf16=dtype != L.F32, lse=lse, bf16_products=(dtype == L.BF16 and ATTN_BWD_BF16))
+                   split_bf16=dtype != L.F32, lse=lse, bf16_products=(dtype == L.BF16 and ATTN_BWD_BF16), drop=drop)
         dbias = None
         if want_dbias:
             dbias = _f32(tuple(bias.shape), dev)
@@ -802,8 +816,10 @@ def layernorm_train(ln: LayerNorm, x2d):
 
 def feedforward_train(ff: FeedForwardSeq, x2d, dtype, img=None):
     ln, lin1, lin2 = ff[0], ff[1], ff[4]
-    assert ff[3].p == 0., 'the training kernels are built for ff_dropout = 0 (the reference default)'
-    return _FFBlock.apply(x2d, ln.weight, ln.bias, lin1.weight, lin2.weight, dtype, ln.eps, img)
+    drop = L.DropSite.of(ff[3], x2d.device)                             # ff_dropout: active iff the module is in training mode and p > 0
+    if drop is None:
+        return _FFBlock.apply(x2d, ln.weight, ln.bias, lin1.weight, lin2.weight, dtype, ln.eps, img)
+    return _FFBlock.apply(x2d, ln.weight, ln.bias, lin1.weight, lin2.weight, dtype, ln.eps, img, drop)
 
 
 def peg_train(peg: PEG, x2d, shape):
@@ -811,11 +827,11 @@ def peg_train(peg: PEG, x2d, shape):
 
 
 def attention_train(attn: Attention, x2d, S, n, dtype, *, context2d=None, n_ctx=None, attn_bias=None, kmask=None, img=None):
-    assert attn.attn_dropout.p == 0., 'the training kernels are built for attn_dropout = 0 (the reference default)'
+    drop = L.DropSite.of(attn.attn_dropout, x2d.device)                 # attn_dropout: active iff the module is in training mode and p > 0
     assert not (attn.causal and context2d is not None), 'causal attention is self-attention (attention.py:166-172)'
     cn = attn.context_norm if isinstance(attn.context_norm, LayerNorm) else None
     slopes = attn.rel_pos_bias.slopes.reshape(-1).contiguous() if attn.causal else None     # ALiBi + causal mask inside the kernels
-    meta = (dtype, S, n, n_ctx, attn.heads, float(attn.scale), attn.norm.eps, slopes, img)
+    meta = (dtype, S, n, n_ctx, attn.heads, float(attn.scale), attn.norm.eps, slopes, drop, img)
     return _AttnBlock.apply(x2d, context2d, attn.norm.gamma, attn.norm.beta, cn.gamma if (cn is not None and context2d is not None) else None,
                             cn.beta if cn is not None else None, attn.to_q.weight, attn.to_kv.weight, attn.null_kv, attn.q_scale, attn.k_scale,
                             attn.to_out.weight, attn_bias, kmask, meta)
