@@ -252,18 +252,17 @@ int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void* Vt, const
                 int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
                 int out_is_f32, int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len,
                 const int* pos_code, int code_off, int tab_run4, float score_bound, void* stream);
+/* a dropout site of the training kernels (the dropout paragraph further down): stream (seed, offset), keep_thr in [1, 256], scale = 1 / (1 - keep_thr / 256).
+ * Every entry point that takes one takes NULL for no dropout. */
+typedef struct pk_dropout { unsigned long long seed, offset; int keep_thr; float scale; } pk_dropout;
 /* The training forward (attention.py:157-182 under autograd): the same product, and lse[(s h + hh) nq + i] = log sum_j exp(score row i) for the
- * backward kernels (pk_attn_bwd with bit 1 of its flag word set skips the pass that recomputed it).  LDS-free kernel; no bias table / score bound. */
+ * backward kernels (pk_attn_bwd_ws with bit 1 of its flag word set skips the pass that recomputed it).  LDS-free kernel; no bias table / score bound.
+ * drop = attn_dropout (attention.py:177): the softmax statistics and lse are those of the undropped probabilities, the P that multiplies V is masked
+ * by the keep function of (seed, offset) and O is scaled by `scale`.  With a site every shape runs on the LDS-free kernel (the LDS-staged forms serve
+ * p = 0 only) and S h nq <= 2^32 - 1.  pk_attn_bwd_ws with the same site is its backward. */
 int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
                     int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
-                    int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse, void* stream);
-/* pk_attn_fwd_lse with attn_dropout (attention.py:177; the dropout paragraph further down): the softmax statistics and lse are those of the undropped
- * probabilities, the P that multiplies V is masked by the keep function of (seed, offset) and O is scaled by `scale`.  Every shape runs on the
- * LDS-free kernel (the LDS-staged forms serve p = 0 only).  pk_attn_bwd_drop_ws is its backward. */
-int pk_attn_fwd_lse_drop(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
-                         int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
-                         int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse,
-                         unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream);
+                    int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse, const pk_dropout* drop, void* stream);
 /* score_bound: an upper bound of sim + bias over every (head, query, key), or NaN.  q^ and k^ are unit vectors times q_scale / k_scale,
  * so |sim| <= scale * max_d |q_scale_d k_scale_d| and the caller knows the maximum of its bias: with a finite bound (and no key
  * mask, not causal, bf16, >= 64 queries and keys) the softmax numerators are p = 2^(s log2(e) - ceil(bound log2(e))) -- no running
@@ -372,9 +371,11 @@ int pk_colsum(const float* src, long long ld, int M, int N, float scale, float* 
 int pk_ln_bwd_parts(int M);
 int pk_layernorm_bwd(const float* x, long long ldx, const float* gamma, const float* dy, long long lddy, const float* add, long long ldadd,
                      float* dx, long long lddx, float* pg, float* pb, float eps, int M, int D, void* stream);
-/* GEGLU on stored pre-activations h (M, >= goff + F): out = h[:, :F] * gelu(h[:, goff : goff + F]) (attention.py:40-43), and its backward */
-int pk_geglu(const float* h, long long ldh, int goff, float* out, long long ldo, int M, int F, void* stream);
-int pk_geglu_bwd(const float* h, long long ldh, int goff, const float* dout, long long ldd, float* dh, long long lddh, int M, int F, void* stream);
+/* GEGLU on stored pre-activations h (M, >= goff + F): out = h[:, :F] * gelu(h[:, goff : goff + F]) (attention.py:40-43), and its backward.
+ * drop = ff_dropout: out = geglu(h) o m * scale in the same pass; pk_geglu_bwd: dout o m * scale in front of the GEGLU derivative. */
+int pk_geglu(const float* h, long long ldh, int goff, float* out, long long ldo, int M, int F, const pk_dropout* drop, void* stream);
+int pk_geglu_bwd(const float* h, long long ldh, int goff, const float* dout, long long ldd, float* dh, long long lddh, int M, int F, const pk_dropout* drop,
+                 void* stream);
 /* ---- dropout of the training kernels (attention.py:45-52 ff_dropout behind GEGLU, attention.py:177 attn_dropout on the softmax probabilities).
  * A dropout site is a stream (seed, offset); whether element (row, col) of the site survives is a pure function of (seed, offset, row, col)
  * (csrc/common.hpp drop_keys / drop_row / drop_word / drop_keep; NumPy mirror phenaki_pytorch_amd/dropout.py), so masks are regenerated in the
@@ -382,13 +383,8 @@ int pk_geglu_bwd(const float* h, long long ldh, int goff, const float* dout, lon
  * col = j over the nnull + n_kv keys (null keys first); feed-forward row = token row, col over the inner width.  An element is dropped iff its 8-bit
  * draw < keep_thr (p_eff = keep_thr / 256); survivors are multiplied by `scale`, which the host computes as 1 / (1 - p_eff) in ONE place
  * (dropout.py quantize).  keep_thr in [1, 256] for the kernels that apply a mask.  Statistically equivalent to torch's nn.Dropout, not its stream.
- * pk_dropout_mask: out (rows, cols) bytes, 1 = keep, for the index range [0, rows) x [0, cols) (keep_thr in [0, 256]; rows < 2^32).
- * pk_geglu_drop: out = geglu(h) o m * scale in the pass of pk_geglu; pk_geglu_bwd_drop: dout o m * scale in front of the GEGLU derivative. */
+ * pk_dropout_mask: out (rows, cols) bytes, 1 = keep, for the index range [0, rows) x [0, cols) (keep_thr in [0, 256]; rows < 2^32). */
 int pk_dropout_mask(unsigned long long seed, unsigned long long offset, int keep_thr, long long rows, int cols, unsigned char* out, void* stream);
-int pk_geglu_drop(const float* h, long long ldh, int goff, float* out, long long ldo, int M, int F, unsigned long long seed, unsigned long long offset,
-                  int keep_thr, float scale, void* stream);
-int pk_geglu_bwd_drop(const float* h, long long ldh, int goff, const float* dout, long long ldd, float* dh, long long lddh, int M, int F,
-                      unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream);
 /* dz = dy * (y > 0 ? 1 : slope): LeakyReLU backward from the activation's output (position-bias MLP, attention.py:243-247) */
 /* the tokenizer's reconstruction step (cvivit.py:585-591 under autograd; the LFQ's straight-through estimator):
  * pk_scaled_diff: out = (a - b) * scale (* *scale_dev when given) over n floats (n % 4 == 0) -- d/da of (scale / 2) sum (a - b)^2;
@@ -438,7 +434,7 @@ int pk_adamw(float* p, const float* g, float* m, float* v, float lr, float beta1
 int pk_adamw_multi(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step, void* stream);
 /* attention backward (attention.py:132-182).  pk_attn_train_prep: the f32 operands q^ = l2norm(q) q_scale scale -> Qh (S heads, n, 64),
  * k^ = l2norm([null_k ; k]) k_scale -> Kh, [null_v ; v] -> Vh (S heads, nnull + n_kv, 64) from the projection outputs q (S n, ldq), kv (S n_kv, ldkv).
- * pk_attn_bwd: dQh / dKh / dVh from those, the forward output O (f32 or bf16) and dO; bias (heads, n, n_kv) / kmask (S, n_kv) cover the real keys;
+ * pk_attn_bwd_ws: dQh / dKh / dVh from those, the forward output O (f32 or bf16) and dO; bias (heads, n, n_kv) / kmask (S, n_kv) cover the real keys;
  * dS (S heads, n, n_kv; optional) = the score gradient for the position-bias gradient (pk_sum_batch over S); lse / Drow: (S heads n) scratch;
  *   causal (attention.py:166-172, the C-ViViT temporal transformers): ALiBi slopes [heads] over all nnull + n keys and the causal mask;
  *   split_bf16: a flag word -- bit 0: the tile products on the bf16 matrix cores from (hi, lo) splits of the f32 operands (the bf16x3 / bf16 modes),
@@ -451,22 +447,16 @@ int pk_attn_train_prep(const float* q, long long ldq, const float* kv, long long
 int pk_attn_train_prep_bwd(const float* q, long long ldq, const float* kv, long long ldkv, const float* null_kv, const float* q_scale, const float* k_scale,
                            float scale, const float* dQh, const float* dKh, const float* dVh, float* dq, long long lddq, float* dkv, long long lddkv,
                            float* pq, float* pk, float* dnull, int S, int heads, int n, int n_kv, int nnull, void* stream);
-int pk_attn_bwd(const float* Qh, const float* Kh, const float* Vh, const void* O, long long ldo, int o_bf16, const float* dO, long long lddo,
-                const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, void* stream);
-/* the same with a workspace of pk_attn_bwd_work(...) floats (0: none needed): with few key tiles (cross-attention on 14 keys: one tile per head) the
- * query tiles of a key tile are dealt to several workgroups whose partial dK^ / dV slabs are added in index order (deterministic). */
+/* work: a workspace of pk_attn_bwd_work(...) floats (0: none needed, NULL): with few key tiles (cross-attention on 14 keys: one tile per head) the
+ * query tiles of a key tile are dealt to several workgroups whose partial dK^ / dV slabs are added in index order (deterministic).
+ * drop: the site pk_attn_fwd_lse ran with (attention.py:177 under autograd): dP = (dO V^T) o m * scale, dS = P o (dP - D) with D = rowsum(dO o O) of
+ * the dropped O, dV = (P o m * scale)^T dO; the optional dS output carries the mask too.  All three product forms of the flag word; the packed
+ * short-sequence layout is not used; S heads n <= 2^32 - 1. */
 int pk_attn_bwd_work(int S, int heads, int n, int n_kv, int nnull);
 int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long long ldo, int o_bf16, const float* dO, long long lddo,
                    const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                   float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long long work_floats, void* stream);
-/* pk_attn_bwd_ws behind pk_attn_fwd_lse_drop with the same (seed, offset, keep_thr, scale) (attention.py:177 under autograd): dP = (dO V^T) o m * scale,
- * dS = P o (dP - D) with D = rowsum(dO o O) of the dropped O, dV = (P o m * scale)^T dO; the optional dS output carries the mask too.  All three
- * product forms of the flag word; the packed short-sequence layout is not used. */
-int pk_attn_bwd_drop_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long long ldo, int o_bf16, const float* dO, long long lddo,
-                        const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                        float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long long work_floats,
-                        unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream);
+                   float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long long work_floats,
+                   const pk_dropout* drop, void* stream);
 
 /* ---- the tokenizer's adversarial branch: cvivit.py:59-213 (Discriminator), :604-671 (hinge / gradient penalty / adaptive weight).
  * Images are CHANNELS-LAST pixel rows x[(b, y, x)][c] (f32, C % 4 == 0), so every nn.Conv2d (cvivit.py:115-127, 191) is pk_gemm on a patch matrix:

@@ -59,8 +59,7 @@ SIGNATURES = {
     'pk_qkv_attn': [_I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _L, _I, _P, _I, _P, _I, _P, _P],
     'pk_q_attn_cached': [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P],
     'pk_attn_fwd': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P],
-    'pk_attn_fwd_lse': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    'pk_attn_fwd_lse_drop': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _ULL, _ULL, _I, _F, _P],
+    'pk_attn_fwd_lse': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'pk_attn_small': [_P, _I, _P, _I, _P, _P, _F, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'pk_cfg_mix': [_P, _I, _I, _I, _I, _P, _I, _F, _I, _P, _I, _I, _I, _P],
     'pk_vocab_ntiles': [_I],
@@ -77,11 +76,9 @@ SIGNATURES = {
     'pk_colsum': [_P, _LL, _I, _I, _F, _P, _I, _P, _P],
     'pk_ln_bwd_parts': [_I],
     'pk_layernorm_bwd': [_P, _LL, _P, _P, _LL, _P, _LL, _P, _LL, _P, _P, _F, _I, _I, _P],
-    'pk_geglu': [_P, _LL, _I, _P, _LL, _I, _I, _P],
-    'pk_geglu_bwd': [_P, _LL, _I, _P, _LL, _P, _LL, _I, _I, _P],
+    'pk_geglu': [_P, _LL, _I, _P, _LL, _I, _I, _P, _P],
+    'pk_geglu_bwd': [_P, _LL, _I, _P, _LL, _P, _LL, _I, _I, _P, _P],
     'pk_dropout_mask': [_ULL, _ULL, _I, _LL, _I, _P, _P],
-    'pk_geglu_drop': [_P, _LL, _I, _P, _LL, _I, _I, _ULL, _ULL, _I, _F, _P],
-    'pk_geglu_bwd_drop': [_P, _LL, _I, _P, _LL, _P, _LL, _I, _I, _ULL, _ULL, _I, _F, _P],
     'pk_leaky_bwd': [_P, _LL, _P, _LL, _P, _LL, _I, _I, _F, _P],
     'pk_scaled_diff': [_P, _P, _F, _P, _P, _LL, _P],
     'pk_sign': [_P, _F, _P, _LL, _P],
@@ -105,10 +102,8 @@ SIGNATURES = {
     'pk_gemm_splitk': [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     'pk_adamw': [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _LL, _P],
     'pk_adamw_multi': [_P, _I, _F, _F, _F, _F, _F, _I, _P],
-    'pk_attn_bwd': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    'pk_attn_bwd_ws': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
+    'pk_attn_bwd_ws': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P, _P],
     'pk_attn_bwd_work': [_I, _I, _I, _I, _I],
-    'pk_attn_bwd_drop_ws': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _ULL, _ULL, _I, _F, _P],
     'pk_im2col': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
     'pk_col2im': [_P, _LL, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     'pk_nchw_to_rows': [_P, _I, _I, _I, _I, _I, _P, _P],
@@ -465,24 +460,18 @@ def attn_fwd(dtype, Qp, Kp, Vt, O, S, h, nq, n_kv, nnull, *, bias=None, kmask=No
              score_bound=None, lse=None, drop=None):
     """bias: full (h, nq, n_kv) f32 tensor, or bias_table = (tab (h, L) f32, pos_code (n,) int32, offset, ...): the relative-position
     form.  score_bound: upper bound of sim + bias (python float) -> fixed-offset softmax; None: running-max flash loop.
-    lse ((S h nq,) f32; the training forward): also write every row's log-sum-exp for pk_attn_bwd."""
+    lse ((S h nq,) f32; the training forward): also write every row's log-sum-exp for pk_attn_bwd_ws."""
     tab, codes, off = bias_table[:3] if bias_table is not None else (None, None, 0)
     run4 = 1 if (bias_table is not None and len(bias_table) > 5 and bias_table[5]) else 0
     if bias is not None:
         bh, bld = bias.stride(0), bias.stride(1)
     else:
         bh, bld = 0, 0
-    if drop is not None:                                                  # attn_dropout > 0: a DropSite (seed, offset, thr, scale)
+    if lse is not None or drop is not None:                               # the training forward; drop: the DropSite of attn_dropout > 0
         assert lse is not None and bias_table is None and score_bound is None
-        rc = load().pk_attn_fwd_lse_drop(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
-                                         1 if causal else 0, ptr(O), O.stride(-2), 1 if O.dtype == torch.float32 else 0, S, h, nq, n_kv, nnull, ptr(lse),
-                                         drop.seed, drop.offset, drop.thr, drop.scale, stream(O))
-        _check(rc, 'pk_attn_fwd_lse_drop')
-        return
-    if lse is not None:
-        assert bias_table is None and score_bound is None
         rc = load().pk_attn_fwd_lse(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
-                                    1 if causal else 0, ptr(O), O.stride(-2), 1 if O.dtype == torch.float32 else 0, S, h, nq, n_kv, nnull, ptr(lse), stream(O))
+                                    1 if causal else 0, ptr(O), O.stride(-2), 1 if O.dtype == torch.float32 else 0, S, h, nq, n_kv, nnull, ptr(lse),
+                                    _site(drop), stream(O))
         _check(rc, 'pk_attn_fwd_lse')
         return
     rc = load().pk_attn_fwd(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
@@ -571,6 +560,16 @@ class PackJob(ctypes.Structure):
     """include/phenaki_hip.h PkPackJob"""
     _fields_ = [('src', ctypes.c_void_p), ('out', ctypes.c_void_p), ('lds', ctypes.c_longlong), ('ldo', ctypes.c_longlong), ('R', ctypes.c_int),
                 ('K', ctypes.c_int), ('Kp', ctypes.c_int), ('flags', ctypes.c_int), ('tile0', ctypes.c_int), ('tiles_x', ctypes.c_int)]
+
+
+class Dropout(ctypes.Structure):
+    """include/phenaki_hip.h pk_dropout"""
+    _fields_ = [('seed', ctypes.c_ulonglong), ('offset', ctypes.c_ulonglong), ('keep_thr', ctypes.c_int), ('scale', ctypes.c_float)]
+
+
+def _site(drop):
+    """the pk_dropout argument of a DropSite (None: no dropout)"""
+    return ctypes.byref(drop.c) if drop is not None else None
 
 
 class SumJob(ctypes.Structure):
@@ -681,25 +680,15 @@ def layernorm_bwd(x, gamma, dy, dx, M, D, *, add=None, want_beta=False, eps=1e-5
     return (out[:D], out[D:]) if want_beta else (out, None)
 
 
-def geglu(h, goff, out, M, F):
-    rc = load().pk_geglu(ptr(h), h.stride(-2), goff, ptr(out), out.stride(-2), M, F, stream(h))
+def geglu(h, goff, out, M, F, drop=None):
+    """drop: the DropSite of ff_dropout > 0 (out = geglu(h) o m / (1 - p_eff)), None: no dropout; geglu_bwd takes the forward's"""
+    rc = load().pk_geglu(ptr(h), h.stride(-2), goff, ptr(out), out.stride(-2), M, F, _site(drop), stream(h))
     _check(rc, 'pk_geglu')
 
 
-def geglu_bwd(h, goff, dout, dh, M, F):
-    rc = load().pk_geglu_bwd(ptr(h), h.stride(-2), goff, ptr(dout), dout.stride(-2), ptr(dh), dh.stride(-2), M, F, stream(h))
+def geglu_bwd(h, goff, dout, dh, M, F, drop=None):
+    rc = load().pk_geglu_bwd(ptr(h), h.stride(-2), goff, ptr(dout), dout.stride(-2), ptr(dh), dh.stride(-2), M, F, _site(drop), stream(h))
     _check(rc, 'pk_geglu_bwd')
-
-
-def geglu_drop(h, goff, out, M, F, drop):
-    rc = load().pk_geglu_drop(ptr(h), h.stride(-2), goff, ptr(out), out.stride(-2), M, F, drop.seed, drop.offset, drop.thr, drop.scale, stream(h))
-    _check(rc, 'pk_geglu_drop')
-
-
-def geglu_bwd_drop(h, goff, dout, dh, M, F, drop):
-    rc = load().pk_geglu_bwd_drop(ptr(h), h.stride(-2), goff, ptr(dout), dout.stride(-2), ptr(dh), dh.stride(-2), M, F,
-                                  drop.seed, drop.offset, drop.thr, drop.scale, stream(h))
-    _check(rc, 'pk_geglu_bwd_drop')
 
 
 def dropout_mask(seed, offset, rows, cols, p, device):
@@ -727,6 +716,7 @@ class DropSite:
         gen.set_offset(self.offset + 4)
         self.p = float(p)
         self.thr, self.p_eff, self.scale = quantize(p)
+        self.c = Dropout(self.seed, self.offset, self.thr, self.scale)
 
     @staticmethod
     def of(module, device):
@@ -837,7 +827,8 @@ def attn_train_prep_bwd(q, kv, null_kv, q_scale, k_scale, scale, dQh, dKh, dVh, 
 
 def attn_bwd(Qh, Kh, Vh, O, dO, dQh, dKh, dVh, S, h, n, n_kv, nnull, *, bias=None, kmask=None, dS=None, slopes=None, causal=False, split_bf16=False, lse=None,
              bf16_products=False, drop=None):
-    """lse ((S h n,) f32 from attn_fwd(lse=...)): the backward skips its own log-sum-exp pass.  bf16_products: single bf16 MFMA products (the bf16 mode)"""
+    """lse ((S h n,) f32 from attn_fwd(lse=...)): the backward skips its own log-sum-exp pass.  bf16_products: single bf16 MFMA products (the bf16 mode).
+    drop: the forward's DropSite (the mask is regenerated)"""
     dev = Qh.device
     flags = (1 if split_bf16 else 0) | (2 if lse is not None else 0) | (4 if bf16_products else 0)
     if lse is None:
@@ -845,17 +836,10 @@ def attn_bwd(Qh, Kh, Vh, O, dO, dQh, dKh, dVh, S, h, n, n_kv, nnull, *, bias=Non
     drow = torch.empty((S * h * n,), device=dev, dtype=torch.float32)
     nwork = load().pk_attn_bwd_work(S, h, n, n_kv, nnull)                  # few key tiles: partial dK / dV slabs of the query-tile groups
     work = torch.empty((nwork,), device=dev, dtype=torch.float32) if nwork > 0 else None
-    if drop is not None:                                                  # the forward's DropSite: the mask is regenerated
-        rc = load().pk_attn_bwd_drop_ws(ptr(Qh), ptr(Kh), ptr(Vh), ptr(O), O.stride(-2), 1 if O.dtype == torch.bfloat16 else 0, ptr(dO), dO.stride(-2), ptr(bias),
-                                        ptr(kmask), f32p(slopes, 'ALiBi slopes') if causal else None, 1 if causal else 0, ptr(dQh), ptr(dKh), ptr(dVh), ptr(dS),
-                                        ptr(lse), ptr(drow), S, h, n, n_kv, nnull, flags, ptr(work), nwork if nwork > 0 else 0,
-                                        drop.seed, drop.offset, drop.thr, drop.scale, stream(Qh))
-        _check(rc, 'pk_attn_bwd_drop_ws')
-        return
     rc = load().pk_attn_bwd_ws(ptr(Qh), ptr(Kh), ptr(Vh), ptr(O), O.stride(-2), 1 if O.dtype == torch.bfloat16 else 0, ptr(dO), dO.stride(-2), ptr(bias), ptr(kmask),
                                f32p(slopes, 'ALiBi slopes') if causal else None, 1 if causal else 0, ptr(dQh), ptr(dKh), ptr(dVh), ptr(dS), ptr(lse), ptr(drow), S, h, n, n_kv, nnull, flags,
-                               ptr(work), nwork if nwork > 0 else 0, stream(Qh))
-    _check(rc, 'pk_attn_bwd')
+                               ptr(work), nwork if nwork > 0 else 0, _site(drop), stream(Qh))
+    _check(rc, 'pk_attn_bwd_ws')
 
 
 def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):

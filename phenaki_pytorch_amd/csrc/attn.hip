@@ -934,13 +934,38 @@ extern "C" int pk_debug_attn_timeline(unsigned long long* out, int n, int clear)
 }
 #endif
 
+// compute units of the current device (256 when the query fails), asked once
+static int n_cu() {
+    static const int n = [] { int dev = 0, cus = 256; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256; return cus > 0 ? cus : 256; }();
+    return n;
+}
+
+// the LDS-free kernel for (dtype, QF query fragments per wave), without (DROP = false) or with attn_dropout
+template <bool DROP>
+static int attn_fwd_launch(int dtype, int QF, bool images_ok, dim3 grid, dim3 block, hipStream_t s, const AttnArgs& a, const DropParam<DROP>& dr) {
+    if (dtype == 1) {
+        if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4, DROP>), grid, block, 0, s, a, dr);
+        else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2, DROP>), grid, block, 0, s, a, dr);
+        else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1, DROP>), grid, block, 0, s, a, dr);
+    } else if (dtype == 0) {
+        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2, DROP>), grid, block, 0, s, a, dr);
+        else hipLaunchKernelGGL((attn_fwd_kernel<float, 1, DROP>), grid, block, 0, s, a, dr);
+    } else if (dtype == 2) {
+        if (!images_ok) return PK_EINVAL;
+        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2, DROP>), grid, block, 0, s, a, dr);
+        else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1, DROP>), grid, block, 0, s, a, dr);
+    } else return PK_EINVAL;
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
 static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* Vt,
                          const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                          const float* slopes, int causal, void* O, int ldo, int out_is_f32,
                          int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len, const int* pos_code,
-                         int code_off, int tab_run4, float score_bound, float* lse, void* stream, const DropArgs* drop = nullptr) {
+                         int code_off, int tab_run4, float score_bound, float* lse, const pk_dropout* drop, void* stream) {
     if (!Qp || !Kp || !Vt || !O || S <= 0 || h <= 0) return PK_EINVAL;
-    if (drop && (!lse || bias_tab || (unsigned long long)S * h * nq > 0xFFFFFFFFull)) return PK_EINVAL;
+    if (drop && (!lse || bias_tab || drop_site_bad(drop) || (unsigned long long)S * h * nq > 0xFFFFFFFFull)) return PK_EINVAL;
     if (bias_tab && (bias || !pos_code || tab_len <= 0 || nnull != 0 || nq != n_kv || causal || kmask)) return PK_EINVAL;
     if (ldo & 3) return PK_EALIGN;
     int nq_pad, nk_pad;
@@ -970,9 +995,8 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         // round of workgroups (3 per CU with the bias table in LDS) the 128-row workgroups win: S*h = 128, n = 576: 26.6 vs 35.8 us
         // (table), 23.4 vs 29.9 (no bias); S*h = 96: 21.6 vs 30.1; at S*h <= 64 one round either way and 16 rows win (18.8 vs 20.5 us)
         const bool fix = score_bound == score_bound && fabsf(score_bound) < 1e4f && !kmask && !causal && !bias;
-        static const int n_cu = [] { int dev = 0, cus = 256; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256; return cus > 0 ? cus : 256; }();
         const long wgs16 = (long)S * h * ((nq_pad + 63) / 64);
-        const int qf = ((lds_qf == 2 || (fix && lds_qf != 1 && wgs16 > 3L * n_cu)) && nq >= 128) ? 2 : 1;
+        const int qf = ((lds_qf == 2 || (fix && lds_qf != 1 && wgs16 > 3L * n_cu())) && nq >= 128) ? 2 : 1;
         const bool pf = pf_env >= 0 ? pf_env != 0 : (qf == 1 && nk_pad >= 192);
         const int qblocks = (nq_pad + 64 * qf - 1) / (64 * qf);
         const uint32_t kv_bytes = (uint32_t)((size_t)S * h * nk_pad * 128);
@@ -1050,10 +1074,9 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
             }
             // one workgroup per CU (the 64 KB ring, one wave per SIMD): 128-row workgroups are 5 per head at n = 576, i.e. 320 for the 64 (sequence, head)
             // pairs of a B = 8 step = two rounds on 256 CUs; 192-row workgroups (48 rows per wave) are 192 = one round
-            static const int n_cu = [] { int dev = 0, cus = 256; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256; return cus > 0 ? cus : 256; }();
             static const int qf_env = [] { const char* e = getenv("PK_ATTN_TRAIN_QF"); return e ? atoi(e) : 0; }();
             const long wg2 = (long)S * h * ((nq_pad + 127) / 128), wg3 = (long)S * h * ((nq_pad + 191) / 192);
-            const bool three = qf_env ? qf_env == 3 : (wg2 > n_cu && wg3 <= n_cu);
+            const bool three = qf_env ? qf_env == 3 : (wg2 > n_cu() && wg3 <= n_cu());
             if (three) hipLaunchKernelGGL((attn_fwd_lds_kernel<3, false, false, false, bf16x3p>), dim3((unsigned)wg3), block, (size_t)2 * 32768, s, a,
                                           (uint32_t)((size_t)S * h * nk_pad * 256));
             else hipLaunchKernelGGL((attn_fwd_lds_kernel<2, false, false, false, bf16x3p>), dim3((unsigned)wg2), block, (size_t)2 * 32768, s, a,
@@ -1063,36 +1086,9 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         }
     }
     if (bias_tab) return PK_EINVAL;                       // the table form exists in the LDS-staged kernel only
-    if (drop) {
-        if (dtype == 1) {
-            if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-            else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-            else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-        } else if (dtype == 0) {
-            if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-            else hipLaunchKernelGGL((attn_fwd_kernel<float, 1, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-        } else if (dtype == 2) {
-            if (!out_is_f32 || ((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) return PK_EINVAL;
-            if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-            else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1, true>), grid, block, 0, s, a, DropParam<true>(*drop));
-        } else return PK_EINVAL;
-        PK_CHECK_LAUNCH();
-        return PK_OK;
-    }
-    if (dtype == 1) {
-        if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4>), grid, block, 0, s, a, DropParam<false>{});
-        else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2>), grid, block, 0, s, a, DropParam<false>{});
-        else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1>), grid, block, 0, s, a, DropParam<false>{});
-    } else if (dtype == 0) {
-        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2>), grid, block, 0, s, a, DropParam<false>{});
-        else hipLaunchKernelGGL((attn_fwd_kernel<float, 1>), grid, block, 0, s, a, DropParam<false>{});
-    } else if (dtype == 2) {
-        if (!out_is_f32 || ((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) return PK_EINVAL;
-        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2>), grid, block, 0, s, a, DropParam<false>{});
-        else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1>), grid, block, 0, s, a, DropParam<false>{});
-    } else return PK_EINVAL;
-    PK_CHECK_LAUNCH();
-    return PK_OK;
+    const bool images_ok = out_is_f32 && !((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127);   // what dtype 2 needs
+    return drop ? attn_fwd_launch<true>(dtype, QF, images_ok, grid, block, s, a, DropParam<true>(drop_keys(*drop)))
+                : attn_fwd_launch<false>(dtype, QF, images_ok, grid, block, s, a, DropParam<false>{});
 }
 
 extern "C" int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void* Vt,
@@ -1101,34 +1097,23 @@ extern "C" int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void
                            int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len, const int* pos_code,
                            int code_off, int tab_run4, float score_bound, void* stream) {
     return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, bias_tab, tab_len,
-                         pos_code, code_off, tab_run4, score_bound, nullptr, stream);
+                         pos_code, code_off, tab_run4, score_bound, nullptr, nullptr, stream);
 }
-// the training forward: the same product, which also writes lse (S h, nq) = the log-sum-exp of every score row -- pk_attn_bwd (flags bit 1) then
+// the training forward: the same product, which also writes lse (S h, nq) = the log-sum-exp of every score row -- pk_attn_bwd_ws (flags bit 1) then
 // skips its own pass over the keys for it.  Split-bf16 self-attention without null keys, key mask or causal mask (n >= 128) runs on the LDS-staged
 // kernel in its running-max form (64 or 48 query rows per wave, chosen from the workgroup count and the CU count); every other shape on the
 // LDS-free kernel.  No bias table / fixed-offset form here.
+// drop (NULL: none) is attn_dropout (attention.py:177: dropout on the probabilities between the softmax and attn @ v): lse is that of the undropped
+// scores; element (row (s h + hh) nq + i, column j over the nnull + n_kv keys) of the probabilities is kept iff the keep function of stream
+// (seed, offset) says so (keep_thr in [1, 256]: dropped iff its 8-bit draw < keep_thr) and O is scaled by `scale` = 1 / (1 - keep_thr / 256).
+// With a site every shape runs on the LDS-free kernel.
 extern "C" int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const void* Vt,
                                const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                                const float* slopes, int causal, void* O, int ldo, int out_is_f32,
-                               int S, int h, int nq, int n_kv, int nnull, float* lse, void* stream) {
+                               int S, int h, int nq, int n_kv, int nnull, float* lse, const pk_dropout* drop, void* stream) {
     if (!lse) return PK_EINVAL;
     return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
-                         nullptr, 0, 0, __builtin_nanf(""), lse, stream);
-}
-
-// pk_attn_fwd_lse with attn_dropout (attention.py:177: dropout on the probabilities between the softmax and attn @ v): lse is that of the undropped
-// scores; element (row (s h + hh) nq + i, column j over the nnull + n_kv keys) of the probabilities is kept iff the keep function of stream
-// (seed, offset) says so (keep_thr in [1, 256]: dropped iff its 8-bit draw < keep_thr) and O is scaled by `scale` = 1 / (1 - keep_thr / 256).
-// Every shape runs on the LDS-free kernel.
-extern "C" int pk_attn_fwd_lse_drop(int dtype, const void* Qp, const void* Kp, const void* Vt,
-                                    const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
-                                    const float* slopes, int causal, void* O, int ldo, int out_is_f32,
-                                    int S, int h, int nq, int n_kv, int nnull, float* lse,
-                                    unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream) {
-    if (!lse || keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
-    const DropArgs d = drop_keys(seed, offset, keep_thr, scale);
-    return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
-                         nullptr, 0, 0, __builtin_nanf(""), lse, stream, &d);
+                         nullptr, 0, 0, __builtin_nanf(""), lse, drop, stream);
 }
 
 // attention.py:128-182 for short self-attention sequences (n <= 64, no null keys) straight from the projection outputs:

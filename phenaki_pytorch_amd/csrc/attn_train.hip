@@ -3,7 +3,7 @@
 //   S = q^ k^T + bias (+ key mask),  P = softmax(S),  O = P v_all
 // The forward pass of a training step runs the inference kernels (pk_attn_prep / pk_attn_fwd); what is saved is q, kv (the projection
 // outputs), O and dO.  Backward recomputes the f32 operands (pk_attn_train_prep), then
-//   pk_attn_bwd :  kernel Q (one workgroup per 64 query rows of a head): lse by an online pass over the keys, D = rowsum(dO * O),
+//   pk_attn_bwd_ws: kernel Q (one workgroup per 64 query rows of a head): lse by an online pass over the keys, D = rowsum(dO * O),
 //                  dS = P * (dO V^T - D), dQ^ = dS K^   [+ dS written out for the position-bias gradient]
 //                  kernel KV (one workgroup per 64 keys of a head): dV = P^T dO, dK^ = dS^T Q^ over all query tiles
 //   pk_attn_train_prep_bwd : l2norm / scale / null-key backward -> dq, dkv, dq_scale, dk_scale, dnull_kv
@@ -638,11 +638,6 @@ extern "C" int pk_attn_train_prep_bwd(const float* q, long ldq, const float* kv,
     return PK_OK;
 }
 
-// O: the forward output (M = S n rows, ldo elements per row; o_bf16 = 1: bf16), dO its gradient (f32).  bias (heads, n, n_kv) / kmask (S, n_kv)
-// cover the REAL keys (the nnull leading null keys carry no bias and are never masked, attention.py:151-158).  dS (S heads, n, n_kv) optional.
-// causal (self-attention, attention.py:166-172): ALiBi with slopes [heads] over all nnull + n keys, then key j > nnull + i masked.
-// lse / Drow: (S heads n) f32 scratch.  split_bf16 is a flag word: bit 0 = split-bf16 tile products, bit 1 = lse already holds the log-sum-exp of
-// every score row (written by pk_attn_fwd_lse in the forward pass): kernel Q then skips its own pass over the keys.
 extern "C" int pk_sum_batch_multi(const void* jobs, int count, void* stream);
 namespace { struct SumJobHost { const float* src; float* out; long stride, E4; int S, blk0; }; }   // = PkSumJob (include/phenaki_hip.h)
 
@@ -662,21 +657,47 @@ extern "C" int pk_attn_bwd_work(int S, int heads, int n, int n_kv, int nnull) {
     const int G = kv_split_of(S, heads, n, nnull + n_kv, &chunk);
     return G > 1 ? (int)(2L * G * S * heads * (nnull + n_kv) * 64) : 0;          // G > 1 only below 384 key tiles: < 2^24 floats
 }
+// kernel Q then kernel KV in product form X3 (0: f32, 1: split-bf16, 2: single bf16 products), without (DROP = false) or with attn_dropout.
+// The dynamic-LDS limits of a DROP value's six kernels are raised on its first use.
+template <bool DROP>
+static int attn_bwd_launch(int X3, dim3 gq, dim3 gk, hipStream_t s, const AttnBwdArgs& p, const DropParam<DROP>& dr) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        const void* const kq[3] = {reinterpret_cast<const void*>(&attn_bwd_q_kernel<0, DROP>), reinterpret_cast<const void*>(&attn_bwd_q_kernel<1, DROP>),
+                                   reinterpret_cast<const void*>(&attn_bwd_q_kernel<2, DROP>)};
+        const void* const kk[3] = {reinterpret_cast<const void*>(&attn_bwd_kv_kernel<0, DROP>), reinterpret_cast<const void*>(&attn_bwd_kv_kernel<1, DROP>),
+                                   reinterpret_cast<const void*>(&attn_bwd_kv_kernel<2, DROP>)};
+        for (int i = 0; i < 3; ++i)
+            if (hipFuncSetAttribute(kq[i], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess ||
+                hipFuncSetAttribute(kk[i], hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
+        attr_done = true;
+    }
+    if (X3 == 2) {
+        hipLaunchKernelGGL((attn_bwd_q_kernel<2, DROP>), gq, dim3(256), 4 * TSZ * 4, s, p, dr);
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<2, DROP>), gk, dim3(256), KV_SMEM, s, p, dr);
+    } else if (X3 == 1) {
+        hipLaunchKernelGGL((attn_bwd_q_kernel<1, DROP>), gq, dim3(256), 4 * TSZ * 4, s, p, dr);
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<1, DROP>), gk, dim3(256), KV_SMEM, s, p, dr);
+    } else {
+        hipLaunchKernelGGL((attn_bwd_q_kernel<0, DROP>), gq, dim3(256), 4 * TSZ * 4, s, p, dr);
+        hipLaunchKernelGGL((attn_bwd_kv_kernel<0, DROP>), gk, dim3(256), KV_SMEM, s, p, dr);
+    }
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+// O: the forward output (M = S n rows, ldo elements per row; o_bf16 = 1: bf16), dO its gradient (f32).  bias (heads, n, n_kv) / kmask (S, n_kv)
+// cover the REAL keys (the nnull leading null keys carry no bias and are never masked, attention.py:151-158).  dS (S heads, n, n_kv) optional.
+// causal (self-attention, attention.py:166-172): ALiBi with slopes [heads] over all nnull + n keys, then key j > nnull + i masked.
+// lse / Drow: (S heads n) f32 scratch.  split_bf16 is a flag word: bit 0 = split-bf16 tile products, bit 1 = lse already holds the log-sum-exp of
+// every score row (written by pk_attn_fwd_lse in the forward pass): kernel Q then skips its own pass over the keys.
+// work (pk_attn_bwd_work floats, or NULL): lets kernel KV deal the query tiles of a key tile to several workgroups when there are few key tiles
+// drop (NULL: none): the site the forward gave pk_attn_fwd_lse -- the mask is regenerated, never stored.  O is the forward's (dropped) output; the optional dS
+// carries the mask too.  The packed short-sequence layout is not used with a site.
 extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
                               const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                              float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats, void* stream);
-extern "C" int pk_attn_bwd(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
-                           const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                           float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, void* stream) {
-    return pk_attn_bwd_ws(Qh, Kh, Vh, O, ldo, o_bf16, dO, lddo, bias, kmask, slopes, causal, dQh, dKh, dVh, dS, lse, Drow, S, heads, n, n_kv, nnull, split_bf16,
-                          nullptr, 0, stream);
-}
-// work (pk_attn_bwd_work floats, or NULL): lets kernel KV deal the query tiles of a key tile to several workgroups when there are few key tiles
-static int attn_bwd_impl(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
-                         const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                         float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats, void* stream,
-                         const DropArgs* drop) {
-    if (!Qh || !Kh || !Vh || !O || !dO || !dQh || !dKh || !dVh || !lse || !Drow || S <= 0 || heads <= 0 || n <= 0 || n_kv <= 0 || nnull < 0) return PK_EINVAL;
+                              float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats,
+                              const pk_dropout* drop, void* stream) {
+    if (drop_site_bad(drop) || !Qh || !Kh || !Vh || !O || !dO || !dQh || !dKh || !dVh || !lse || !Drow || S <= 0 || heads <= 0 || n <= 0 || n_kv <= 0 || nnull < 0) return PK_EINVAL;
     if (!al16(Qh) || !al16(Kh) || !al16(Vh) || !al16(dO) || (lddo & 3) || !al16(O) || (ldo & (o_bf16 ? 7 : 3))) return PK_EALIGN;
     if ((long)S * heads > 0x7fffffffL / 64) return PK_EINVAL;
     if (drop && (unsigned long long)S * heads * n > 0xFFFFFFFFull) return PK_EINVAL;
@@ -698,26 +719,6 @@ static int attn_bwd_impl(const float* Qh, const float* Kh, const float* Vh, cons
         p.S = (int)((p.act_groups + p.pack_g - 1) / p.pack_g);
     }
     hipStream_t s = STREAM(stream);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        attr_done = true;
-    }
-    static bool attr_drop_done = false;
-    if (drop && !attr_drop_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        attr_drop_done = true;
-    }
     const int nqt = (p.n + 63) / 64, nktt = (p.nkt + 63) / 64;
     if (work && !p.pack_n) {
         int chunk;
@@ -729,49 +730,12 @@ static int attn_bwd_impl(const float* Qh, const float* Kh, const float* Vh, cons
     }
     const dim3 gq((unsigned)((long)p.S * p.heads * nqt)), gk((unsigned)((long)p.S * p.heads * nktt * (p.kv_split > 1 ? p.kv_split : 1)));
     static const bool split_on = !(getenv("PK_ATTN_BWD_SPLIT") && getenv("PK_ATTN_BWD_SPLIT")[0] == '0');     // A/B switch
-    if (drop) {
-        if (bf16_products) {
-            hipLaunchKernelGGL((attn_bwd_q_kernel<2, true>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<true>(*drop));
-            hipLaunchKernelGGL((attn_bwd_kv_kernel<2, true>), gk, dim3(256), KV_SMEM, s, p, DropParam<true>(*drop));
-        } else if (split_bf16 && split_on) {
-            hipLaunchKernelGGL((attn_bwd_q_kernel<1, true>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<true>(*drop));
-            hipLaunchKernelGGL((attn_bwd_kv_kernel<1, true>), gk, dim3(256), KV_SMEM, s, p, DropParam<true>(*drop));
-        } else {
-            hipLaunchKernelGGL((attn_bwd_q_kernel<0, true>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<true>(*drop));
-            hipLaunchKernelGGL((attn_bwd_kv_kernel<0, true>), gk, dim3(256), KV_SMEM, s, p, DropParam<true>(*drop));
-        }
-    } else if (bf16_products) {
-        hipLaunchKernelGGL((attn_bwd_q_kernel<2>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<false>{});
-        hipLaunchKernelGGL((attn_bwd_kv_kernel<2>), gk, dim3(256), KV_SMEM, s, p, DropParam<false>{});
-    } else if (split_bf16 && split_on) {
-        hipLaunchKernelGGL((attn_bwd_q_kernel<1>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<false>{});
-        hipLaunchKernelGGL((attn_bwd_kv_kernel<1>), gk, dim3(256), KV_SMEM, s, p, DropParam<false>{});
-    } else {
-        hipLaunchKernelGGL((attn_bwd_q_kernel<0>), gq, dim3(256), 4 * TSZ * 4, s, p, DropParam<false>{});
-        hipLaunchKernelGGL((attn_bwd_kv_kernel<0>), gk, dim3(256), KV_SMEM, s, p, DropParam<false>{});
-    }
-    PK_CHECK_LAUNCH();
+    const int X3 = bf16_products ? 2 : (split_bf16 && split_on) ? 1 : 0;
+    if (int rc = drop ? attn_bwd_launch<true>(X3, gq, gk, s, p, DropParam<true>(drop_keys(*drop))) : attn_bwd_launch<false>(X3, gq, gk, s, p, DropParam<false>{})) return rc;
     if (p.kv_split > 1) {                                                // dK^ / dV = the slabs added in index order (one launch for both)
         const long slab = (long)p.S * p.heads * p.nkt * 64;
         SumJobHost jobs[2] = {{work, dKh, slab, slab / 4, p.kv_split, 0}, {work + (long)p.kv_split * slab, dVh, slab, slab / 4, p.kv_split, 0}};
         return pk_sum_batch_multi(jobs, 2, stream);
     }
     return PK_OK;
-}
-extern "C" int pk_attn_bwd_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
-                              const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                              float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats, void* stream) {
-    return attn_bwd_impl(Qh, Kh, Vh, O, ldo, o_bf16, dO, lddo, bias, kmask, slopes, causal, dQh, dKh, dVh, dS, lse, Drow, S, heads, n, n_kv, nnull, split_bf16,
-                         work, work_floats, stream, nullptr);
-}
-// pk_attn_bwd_ws for a forward that ran pk_attn_fwd_lse_drop with the same (seed, offset, keep_thr, scale): the mask is regenerated, never stored.
-// O is the forward's (dropped) output; the optional dS carries the mask too.  The packed short-sequence layout is not used.
-extern "C" int pk_attn_bwd_drop_ws(const float* Qh, const float* Kh, const float* Vh, const void* O, long ldo, int o_bf16, const float* dO, long lddo,
-                                   const float* bias, const unsigned char* kmask, const float* slopes, int causal, float* dQh, float* dKh, float* dVh, float* dS,
-                                   float* lse, float* Drow, int S, int heads, int n, int n_kv, int nnull, int split_bf16, float* work, long work_floats,
-                                   unsigned long long seed, unsigned long long offset, int keep_thr, float scale, void* stream) {
-    if (keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
-    const DropArgs d = drop_keys(seed, offset, keep_thr, scale);
-    return attn_bwd_impl(Qh, Kh, Vh, O, ldo, o_bf16, dO, lddo, bias, kmask, slopes, causal, dQh, dKh, dVh, dS, lse, Drow, S, heads, n, n_kv, nnull, split_bf16,
-                         work, work_floats, stream, &d);
 }

@@ -274,9 +274,13 @@ __device__ __host__ __forceinline__ DropArgs drop_keys(uint64_t seed, uint64_t o
     d.scale = scale;
     return d;
 }
+// a dropout site as the C ABI passes it (= pk_dropout of include/phenaki_hip.h; a NULL site is p = 0): keep_thr must be in [1, 256] where a mask is applied
+struct pk_dropout { unsigned long long seed, offset; int keep_thr; float scale; };
+inline bool drop_site_bad(const pk_dropout* d) { return d && (d->keep_thr < 1 || d->keep_thr > 256); }
+inline DropArgs drop_keys(const pk_dropout& d) { return drop_keys(d.seed, d.offset, d.keep_thr, d.scale); }
 // the last parameter of a kernel with a compile-time DROP flag: nothing at DROP = false (that instantiation is the kernel without dropout), DropArgs at true
 template <bool DROP> struct DropParam {};
-template <> struct DropParam<true> : DropArgs { DropParam(const DropArgs& d) : DropArgs(d) {} };
+template <> struct DropParam<true> : DropArgs { __device__ __host__ DropParam(const DropArgs& d) : DropArgs(d) {} };
 __device__ __host__ __forceinline__ uint32_t drop_row(const DropArgs& d, uint32_t row) { return mix32(row ^ d.k0); }
 // the draws of columns 4 grp .. 4 grp + 3 of the row whose drop_row() is rowh: byte e belongs to column 4 grp + e
 __device__ __host__ __forceinline__ uint32_t drop_word(const DropArgs& d, uint32_t rowh, uint32_t grp) { return mix32(rowh + 0x9e3779b9u * grp + d.k1); }

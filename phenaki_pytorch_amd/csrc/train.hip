@@ -300,62 +300,49 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 __device__ __forceinline__ float gelu_grad(float g) {
     return 0.5f * (1.0f + erff(g * 0.70710678118654752440f)) + g * 0.3989422804014327f * __expf(-0.5f * g * g);
 }
-__global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, long ldh, int goff, float* __restrict__ out, long ldo, int M, int F4, long total) {
+// With a trailing DropArgs (DROP; ff_dropout, attention.py:45-52: Dropout behind GEGLU): out = geglu(h) o m / (1 - p_eff) in the same pass; backward: dout is
+// masked and scaled before the GEGLU derivative.  m = the keep function (common.hpp) at (row, column) -- a thread's 4 columns are one of its groups -- and
+// is regenerated, never stored.  Columns >= F (the pad up to the stored width) are written as zeros.  DR is empty or one DropArgs: the p = 0 instantiation
+// has no argument for it at all (an empty DropParam<false> would still move the hidden kernel arguments behind it).
+template <typename... DR>
+__global__ __launch_bounds__(256) void geglu_kernel(const float* __restrict__ h, long ldh, int goff, float* __restrict__ out, long ldo, int M, int F4, long total,
+                                                    const DR... dr) {
+    constexpr bool DROP = sizeof...(DR) != 0;
+    const DropParam<DROP> d{dr...};
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int c = (int)(idx % F4) * 4;
         const long r = idx / F4;
         const f32x4 xv = *reinterpret_cast<const f32x4*>(h + r * ldh + c), gv = *reinterpret_cast<const f32x4*>(h + r * ldh + goff + c);
-        *reinterpret_cast<f32x4*>(out + r * ldo + c) = f32x4{xv[0] * gelu_erf(gv[0]), xv[1] * gelu_erf(gv[1]), xv[2] * gelu_erf(gv[2]), xv[3] * gelu_erf(gv[3])};
-    }
-}
-__global__ __launch_bounds__(256) void geglu_bwd_kernel(const float* __restrict__ h, long ldh, int goff, const float* __restrict__ dout, long ldd,
-                                                        float* __restrict__ dh, long lddh, int M, int F4, long total) {
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % F4) * 4;
-        const long r = idx / F4;
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(h + r * ldh + c), gv = *reinterpret_cast<const f32x4*>(h + r * ldh + goff + c);
-        const f32x4 dv = *reinterpret_cast<const f32x4*>(dout + r * ldd + c);
-        f32x4 dxv, dgv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            dxv[j] = dv[j] * gelu_erf(gv[j]);
-            dgv[j] = dv[j] * xv[j] * gelu_grad(gv[j]);
-        }
-        *reinterpret_cast<f32x4*>(dh + r * lddh + c) = dxv;
-        *reinterpret_cast<f32x4*>(dh + r * lddh + goff + c) = dgv;
-    }
-}
-
-// ---- the same with ff_dropout (attention.py:45-52: Dropout behind GEGLU): out = geglu(h) o m / (1 - p_eff) in the same pass; backward: dout is masked
-// and scaled before the GEGLU derivative.  m = the keep function (common.hpp) at (row, column) -- a thread's 4 columns are one of its groups -- and is
-// regenerated, never stored.  Columns >= F (the pad up to the stored width) are written as zeros.
-__global__ __launch_bounds__(256) void geglu_drop_kernel(const float* __restrict__ h, long ldh, int goff, float* __restrict__ out, long ldo, int M, int F4, long total,
-                                                         const DropArgs dr) {
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % F4) * 4;
-        const long r = idx / F4;
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(h + r * ldh + c), gv = *reinterpret_cast<const f32x4*>(h + r * ldh + goff + c);
-        const uint32_t w = drop_word(dr, drop_row(dr, (uint32_t)r), (uint32_t)c >> 2);
+        uint32_t w = 0;
+        if constexpr (DROP) w = drop_word(d, drop_row(d, (uint32_t)r), (uint32_t)c >> 2);
         f32x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = drop_keep(dr, w, j) ? xv[j] * gelu_erf(gv[j]) * dr.scale : 0.f;
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (DROP) o[j] = drop_keep(d, w, j) ? xv[j] * gelu_erf(gv[j]) * d.scale : 0.f;    // a dropped element's gelu is not evaluated
+            else o[j] = xv[j] * gelu_erf(gv[j]);
+        }
         *reinterpret_cast<f32x4*>(out + r * ldo + c) = o;
     }
 }
-__global__ __launch_bounds__(256) void geglu_bwd_drop_kernel(const float* __restrict__ h, long ldh, int goff, const float* __restrict__ dout, long ldd,
-                                                             float* __restrict__ dh, long lddh, int M, int F4, long total, const DropArgs dr) {
+template <typename... DR>
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const float* __restrict__ h, long ldh, int goff, const float* __restrict__ dout, long ldd,
+                                                        float* __restrict__ dh, long lddh, int M, int F4, long total, const DR... dr) {
+    constexpr bool DROP = sizeof...(DR) != 0;
+    const DropParam<DROP> d{dr...};
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int c = (int)(idx % F4) * 4;
         const long r = idx / F4;
         const f32x4 xv = *reinterpret_cast<const f32x4*>(h + r * ldh + c), gv = *reinterpret_cast<const f32x4*>(h + r * ldh + goff + c);
         const f32x4 dv = *reinterpret_cast<const f32x4*>(dout + r * ldd + c);
-        const uint32_t w = drop_word(dr, drop_row(dr, (uint32_t)r), (uint32_t)c >> 2);
+        uint32_t w = 0;
+        if constexpr (DROP) w = drop_word(d, drop_row(d, (uint32_t)r), (uint32_t)c >> 2);
         f32x4 dxv, dgv;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float d = drop_keep(dr, w, j) ? dv[j] * dr.scale : 0.f;
-            dxv[j] = d * gelu_erf(gv[j]);
-            dgv[j] = d * xv[j] * gelu_grad(gv[j]);
+            float dj = dv[j];
+            if constexpr (DROP) dj = drop_keep(d, w, j) ? dj * d.scale : 0.f;
+            dxv[j] = dj * gelu_erf(gv[j]);
+            dgv[j] = dj * xv[j] * gelu_grad(gv[j]);
         }
         *reinterpret_cast<f32x4*>(dh + r * lddh + c) = dxv;
         *reinterpret_cast<f32x4*>(dh + r * lddh + goff + c) = dgv;
@@ -846,40 +833,22 @@ extern "C" int pk_layernorm_bwd(const float* x, long ldx, const float* gamma, co
 }
 
 // h (M, >= goff + F) f32: value columns [0, F), gate columns [goff, goff + F);  F % 4 == 0
-extern "C" int pk_geglu(const float* h, long ldh, int goff, float* out, long ldo, int M, int F, void* stream) {
-    if (!h || !out || M <= 0 || F <= 0 || goff < F) return PK_EINVAL;
+// drop (NULL: none) is ff_dropout: stream (seed, offset), keep_thr in [1, 256] (dropped iff the 8-bit draw < keep_thr), scale = 1 / (1 - keep_thr / 256)
+extern "C" int pk_geglu(const float* h, long ldh, int goff, float* out, long ldo, int M, int F, const pk_dropout* drop, void* stream) {
+    if (!h || !out || M <= 0 || F <= 0 || goff < F || drop_site_bad(drop)) return PK_EINVAL;
     if ((F & 3) || (goff & 3) || (ldh & 3) || (ldo & 3) || !al16(h) || !al16(out)) return PK_EALIGN;
     const long total = (long)M * (F >> 2);
-    hipLaunchKernelGGL(geglu_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, out, ldo, M, F >> 2, total);
+    if (drop) hipLaunchKernelGGL(geglu_kernel<DropArgs>, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, out, ldo, M, F >> 2, total, drop_keys(*drop));
+    else hipLaunchKernelGGL(geglu_kernel<>, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, out, ldo, M, F >> 2, total);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
-extern "C" int pk_geglu_bwd(const float* h, long ldh, int goff, const float* dout, long ldd, float* dh, long lddh, int M, int F, void* stream) {
-    if (!h || !dout || !dh || M <= 0 || F <= 0 || goff < F) return PK_EINVAL;
+extern "C" int pk_geglu_bwd(const float* h, long ldh, int goff, const float* dout, long ldd, float* dh, long lddh, int M, int F, const pk_dropout* drop, void* stream) {
+    if (!h || !dout || !dh || M <= 0 || F <= 0 || goff < F || drop_site_bad(drop)) return PK_EINVAL;
     if ((F & 3) || (goff & 3) || (ldh & 3) || (ldd & 3) || (lddh & 3) || !al16(h) || !al16(dout) || !al16(dh)) return PK_EALIGN;
     const long total = (long)M * (F >> 2);
-    hipLaunchKernelGGL(geglu_bwd_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, dout, ldd, dh, lddh, M, F >> 2, total);
-    PK_CHECK_LAUNCH();
-    return PK_OK;
-}
-
-// pk_geglu / pk_geglu_bwd with ff_dropout: stream (seed, offset), keep_thr in [1, 256] (dropped iff the 8-bit draw < keep_thr), scale = 1 / (1 - keep_thr / 256)
-extern "C" int pk_geglu_drop(const float* h, long ldh, int goff, float* out, long ldo, int M, int F, unsigned long long seed, unsigned long long offset,
-                             int keep_thr, float scale, void* stream) {
-    if (!h || !out || M <= 0 || F <= 0 || goff < F || keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
-    if ((F & 3) || (goff & 3) || (ldh & 3) || (ldo & 3) || !al16(h) || !al16(out)) return PK_EALIGN;
-    const long total = (long)M * (F >> 2);
-    hipLaunchKernelGGL(geglu_drop_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, out, ldo, M, F >> 2, total, drop_keys(seed, offset, keep_thr, scale));
-    PK_CHECK_LAUNCH();
-    return PK_OK;
-}
-extern "C" int pk_geglu_bwd_drop(const float* h, long ldh, int goff, const float* dout, long ldd, float* dh, long lddh, int M, int F, unsigned long long seed,
-                                 unsigned long long offset, int keep_thr, float scale, void* stream) {
-    if (!h || !dout || !dh || M <= 0 || F <= 0 || goff < F || keep_thr < 1 || keep_thr > 256) return PK_EINVAL;
-    if ((F & 3) || (goff & 3) || (ldh & 3) || (ldd & 3) || (lddh & 3) || !al16(h) || !al16(dout) || !al16(dh)) return PK_EALIGN;
-    const long total = (long)M * (F >> 2);
-    hipLaunchKernelGGL(geglu_bwd_drop_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, dout, ldd, dh, lddh, M, F >> 2, total,
-                       drop_keys(seed, offset, keep_thr, scale));
+    if (drop) hipLaunchKernelGGL(geglu_bwd_kernel<DropArgs>, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, dout, ldd, dh, lddh, M, F >> 2, total, drop_keys(*drop));
+    else hipLaunchKernelGGL(geglu_bwd_kernel<>, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), h, ldh, goff, dout, ldd, dh, lddh, M, F >> 2, total);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

@@ -9,9 +9,9 @@ Every block of the trunk is ONE torch.autograd.Function whose forward and backwa
     _Embed          token + position embedding (+ gradient_shrink_alpha)       pk_embed            / pk_embed_bwd
     _PEGBlock       x + dsconv(x)                                              pk_peg              / pk_peg_bwd (+ pk_colsum)
     _AttnBlock      x + to_out(attention(norm(x) [, context]))                 pk_layernorm, pk_gemm, pk_attn_prep, pk_attn_fwd
-                                                                               / pk_attn_train_prep, pk_attn_bwd, pk_attn_train_prep_bwd,
+                                                                               / pk_attn_train_prep, pk_attn_bwd_ws, pk_attn_train_prep_bwd,
                                                                                  pk_pack + pk_gemm (dX, dW), pk_layernorm_bwd
-    _FFBlock        x + W2 dropout(geglu(W1 LayerNorm(x)))                     pk_layernorm, pk_gemm, pk_geglu[_drop] / pk_geglu_bwd[_drop], ...
+    _FFBlock        x + W2 dropout(geglu(W1 LayerNorm(x)))                     pk_layernorm, pk_gemm, pk_geglu / pk_geglu_bwd, ...
     _LayerNormFn    norm_out                                                   pk_layernorm        / pk_layernorm_bwd
     _PositionBias   ContinuousPositionBias as (heads, n, n)                    relative-position-table MLP + pk_bias_gather / pk_bias_scatter
     _VocabCrossEntropy   to_logits + cross entropy on the masked rows          pk_vocab_sample, pk_vocab_ce / pk_ce_grad_slab + pk_gemm
@@ -25,9 +25,9 @@ pk_pack_table); the activation transposes of a backward block leave in one launc
 in another (L.reduce_multi); the forward attention hands its log-sum-exp to the backward kernels (pk_attn_fwd_lse); the critic's gumbel sample and
 the cross entropy share one pass over the vocabulary (`_VocabCrossEntropy(shared=...)`).
 Dropout (attn_dropout / ff_dropout of the reference's constructors, attention.py:45-52, :177): active iff the nn.Dropout module is in training
-mode and p > 0, as in torch; the masks are made inside the kernels (pk_attn_fwd_lse_drop / pk_attn_bwd_drop_ws, pk_geglu_drop / pk_geglu_bwd_drop)
+mode and p > 0, as in torch; the masks are made inside the kernels (the `drop` argument of pk_attn_fwd_lse / pk_attn_bwd_ws, pk_geglu / pk_geglu_bwd)
 from a (seed, offset) stream read off the device's default torch generator on the host -- one `L.DropSite` per dropout site per call, kept on the
-autograd ctx so that the backward kernels regenerate the mask (nothing is stored).  Inactive dropout makes exactly the calls of a p = 0 module.
+autograd ctx so that the backward kernels regenerate the mask (nothing is stored).  Inactive dropout passes no site: exactly the calls of a p = 0 module.
 The tokenizer's own reconstruction step is train_cvivit.py.
 """
 import math
@@ -335,10 +335,7 @@ class _FFBlock(torch.autograd.Function):
         h = _f32((M, 2 * Fp), dev)
         L.gemm(dtype, xa if xa is not None else xn, img['w1p'], M, 2 * Fp, D, C=h)
         a = _f32((M, Fp), dev)
-        if drop is None:
-            L.geglu(h, Fp, a, M, Fp)
-        else:                                                            # ff_dropout: a = geglu(h) o m / (1 - p_eff); the dropped a is the operand of dW2
-            L.geglu_drop(h, Fp, a, M, Fp, drop)
+        L.geglu(h, Fp, a, M, Fp, drop)                                   # ff_dropout: a = geglu(h) o m / (1 - p_eff); the dropped a is the operand of dW2
         y = _f32((M, D), dev)
         L.gemm(dtype, a_operand(dtype, a), img['w2'], M, D, Fp, C=y, res=x)
         ctx.save_for_backward(x, ln_w, w1, w2, xn, h, a)
@@ -369,10 +366,7 @@ class _FFBlock(torch.autograd.Function):
             _weight_grad_gemm(dtype, dyT, aT, D, F, Mp, dW2, sums)
         # ---- GEGLU
         dh = _f32((M, 2 * Fp), dev)
-        if ctx.drop is None:
-            L.geglu_bwd(h, Fp, da, dh, M, Fp)
-        else:                                                            # da o m / (1 - p_eff) in front of the GEGLU derivative (the mask is regenerated)
-            L.geglu_bwd_drop(h, Fp, da, dh, M, Fp, ctx.drop)
+        L.geglu_bwd(h, Fp, da, dh, M, Fp, ctx.drop)                      # ff_dropout: da o m / (1 - p_eff) in front of the GEGLU derivative (the mask is regenerated)
         # ---- first Linear: dxn = dh W1 (the padded layout, transposed), dW1 = dh^T xn in two row groups (value | gate)
         dhT, xnT, dhA = transposes(dtype, [(dh, 'a'), (xn, 'w')], [dh])   # (2 Fp, Mp), (D, Mp)
         dxn = _f32((M, D), dev)

@@ -237,6 +237,83 @@ def test_feedforward_block_with_dropout(dtype, tol):
     print(f'dropout feed-forward {dtype}: ' + ' '.join(f'{k}={v:.2e}' for k, v in errs.items()))
 
 
+# ---- the unified entry points
+
+def test_entry_points_take_an_optional_site():
+    """pk_geglu, pk_geglu_bwd, pk_attn_fwd_lse and pk_attn_bwd_ws each take the dropout site as an argument: without one the result is the p = 0 float64
+    oracle's, with one the oracle's under dropout.keep_mask (both at the fp32 tolerance of MODES: the operands here are f32); a site whose keep_thr
+    is 0 or 257 is PK_EINVAL and nothing is written; the attention forward with a site but no lse is refused.  Smallest shapes that launch: GEGLU
+    M = 4, F = 8 (stored width 8); attention S = 1, heads = 2, n = n_kv = 20 (one ragged tile)."""
+    import ctypes
+    from types import SimpleNamespace
+    from phenaki_pytorch_amd import _lib as L
+    tol = dict(MODES)['fp32']
+    thr, _, scale_keep = DR.quantize(P_ATTN)
+
+    def site(keep_thr=thr):
+        return SimpleNamespace(c=L.Dropout(SEED, 8, keep_thr, scale_keep))
+    g = torch.Generator().manual_seed(5)
+
+    def refused(call, *outs):
+        for bad in (0, 257):
+            for t in outs:
+                t.fill_(-7.)
+            with pytest.raises(RuntimeError, match='PK_EINVAL'):
+                call(site(bad))
+            torch.cuda.synchronize()
+            assert all(bool((t == -7.).all()) for t in outs), 'a refused call must not launch'
+
+    # GEGLU: h = value | gate
+    M, Fw = 4, 8
+    h, dout = torch.randn(M, 2 * Fw, generator=g), torch.randn(M, Fw, generator=g)
+    hc, dc = h.cuda(), dout.cuda()
+    out, dh = torch.empty(M, Fw, device='cuda'), torch.empty(M, 2 * Fw, device='cuda')
+    keep_ff = torch.from_numpy(DR.keep_mask(SEED, 8, M, Fw, P_ATTN)).double()
+    for drop, m in ((None, torch.ones(M, Fw, dtype=torch.float64)), (site(), keep_ff * scale_keep)):
+        hl = h.double().requires_grad_()
+        ref = hl[:, :Fw] * F.gelu(hl[:, Fw:]) * m
+        ref.backward(dout.double())
+        L.geglu(hc, Fw, out, M, Fw, drop)
+        L.geglu_bwd(hc, Fw, dc, dh, M, Fw, drop)
+        close(out, ref, tol, f'geglu site={drop is not None}')
+        close(dh, hl.grad, tol, f'geglu_bwd site={drop is not None}')
+    refused(lambda d: L.geglu(hc, Fw, out, M, Fw, d), out)
+    refused(lambda d: L.geglu_bwd(hc, Fw, dc, dh, M, Fw, d), dh)
+
+    # attention: the f32 operands of the backward (pk_attn_train_prep) are the oracle's inputs
+    S, H, n = 1, 2, 20
+    q, kv, dO = torch.randn(S * n, H * 64, generator=g).cuda(), torch.randn(S * n, 2 * H * 64, generator=g).cuda(), torch.randn(S * n, H * 64, generator=g).cuda()
+    qs, ks = torch.rand(64, generator=g).cuda() + 0.5, torch.rand(64, generator=g).cuda() + 0.5
+    nq_pad, nk_pad = L.attn_pads(n, n, 0)
+    Qp, Kp, Vt = (torch.empty(S * H * pad * 64, device='cuda') for pad in (nq_pad, nk_pad, nk_pad))
+    L.attn_prep(L.F32, q, kv, None, qs, ks, 8., Qp, Kp, Vt, S, H, n, n, 0)
+    Qh, Kh, Vh = (torch.empty(S * H * n, 64, device='cuda') for _ in range(3))
+    L.attn_train_prep(q, kv, None, qs, ks, 8., Qh, Kh, Vh, S, H, n, n, 0)
+    o, lse = torch.empty(S * n, H * 64, device='cuda'), torch.empty(S * H * n, device='cuda')
+    dQh, dKh, dVh = torch.empty_like(Qh), torch.empty_like(Kh), torch.empty_like(Vh)
+    keep_at = torch.from_numpy(DR.keep_mask(SEED, 8, S * H * n, n, P_ATTN)).reshape(S * H, n, n).double()
+    for drop, m in ((None, torch.ones(S * H, n, n, dtype=torch.float64)), (site(), keep_at * scale_keep)):
+        Ql, Kl, Vl = (t.double().cpu().reshape(S * H, n, 64).requires_grad_() for t in (Qh, Kh, Vh))
+        sim = Ql @ Kl.transpose(1, 2)
+        ref = ((sim.softmax(dim=-1) * m) @ Vl).reshape(S, H, n, 64).permute(0, 2, 1, 3).reshape(S * n, H * 64)
+        ref.backward(dO.double().cpu())
+        L.attn_fwd(L.F32, Qp, Kp, Vt, o, S, H, n, n, 0, lse=lse, drop=drop)
+        L.attn_bwd(Qh, Kh, Vh, o, dO, dQh, dKh, dVh, S, H, n, n, 0, lse=lse, drop=drop)
+        close(o, ref, tol, f'attn_fwd site={drop is not None}')
+        close(lse, sim.logsumexp(dim=-1).reshape(-1), tol, f'lse (of the undropped scores) site={drop is not None}')
+        for got, want, name in ((dQh, Ql, 'dQ'), (dKh, Kl, 'dK'), (dVh, Vl, 'dV')):
+            close(got, want.grad.reshape(S * H * n, 64), tol, f'attn_bwd {name} site={drop is not None}')
+    refused(lambda d: L.attn_fwd(L.F32, Qp, Kp, Vt, o, S, H, n, n, 0, lse=lse, drop=d), o)
+    refused(lambda d: L.attn_bwd(Qh, Kh, Vh, o, dO, dQh, dKh, dVh, S, H, n, n, 0, lse=lse, drop=d), dQh, dKh, dVh)
+    o.fill_(-7.)
+    with pytest.raises(AssertionError):                                  # the binding refuses it ...
+        L.attn_fwd(L.F32, Qp, Kp, Vt, o, S, H, n, n, 0, lse=None, drop=site())
+    rc = L.load().pk_attn_fwd_lse(L.F32, Qp.data_ptr(), Kp.data_ptr(), Vt.data_ptr(), None, 0, 0, None, None, 0, o.data_ptr(), o.stride(0), 1, S, H, n, n, 0,
+                                  None, ctypes.byref(site().c), L.stream(o))
+    torch.cuda.synchronize()
+    assert rc == -1 and bool((o == -7.).all()), '... and so does the library (PK_EINVAL)'
+
+
 # ---- switches
 
 def _transformer_step(tr, x, ctx, G, S, n, n_ctx):

@@ -286,7 +286,7 @@ def test_feedforward_block_gradients(dtype, tol):
 def test_attention_block_gradients(case, dtype, tol):
     """x + Attention(x) (attention.py:89-182): position bias gradient, null keys, key mask, l2norm / learned scales; n = 70 (ragged tiles);
     causal_*: ALiBi over the null + real keys and the causal mask (the C-ViViT temporal transformers: n = 9, and n = 70 across key tiles);
-    *packed*: no null keys and n <= 32 -- pk_attn_bwd packs 64 / n whole (sequence, head) groups into one tile (80 groups of 9 rows = 11 full
+    *packed*: no null keys and n <= 32 -- pk_attn_bwd_ws packs 64 / n whole (sequence, head) groups into one tile (80 groups of 9 rows = 11 full
     tiles + a partial one; 22 groups of 12 rows with a key mask); *_long (round 6): n = 200 >= 128 without a key mask -- the training forward runs on the
     LDS-staged kernels there (split-bf16: running-max form with the bias as a matrix, ragged last key tile) and hands the backward its log-sum-exp"""
     import phenaki_pytorch_amd as P

@@ -189,7 +189,7 @@ def test_attention_block_branches(case, dtype, tol):
     qf3_*: the split-bf16 training forward with 48 query rows per wave (wg2 > n_cu >= wg3), at n = 320 (nq_pad % 48 != 0: the last wave of a
     head reaches 32 rows past it -- the Q fragment rows are clamped there) with and without the bias matrix, and at n = 384 (nq_pad % 48 == 0);
     qf2_wide: 64 rows per wave above n_cu with the backward at kv_split = 1; kv_split_uneven: the backward's query tiles dealt to G workgroups
-    with a short last chunk; keys*: ragged last key tiles with / without null keys, key mask, causal + ALiBi; packed*: pk_attn_bwd's packed
+    with a short last chunk; keys*: ragged last key tiles with / without null keys, key mask, causal + ALiBi; packed*: pk_attn_bwd_ws's packed
     (sequence, head) groups at 64 / n per tile and, with dS wanted (the bias gradient), the unpacked path; cross*: n != n_kv at a tile edge."""
     from phenaki_pytorch_amd.attention import resolve_dtype
     from phenaki_pytorch_amd.train import attention_train
