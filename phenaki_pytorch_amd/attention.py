@@ -240,41 +240,35 @@ class FeedForwardSeq(nn.Sequential):
     """attention.py:45-53 : Sequential(nn.LayerNorm, Linear(d, 2*inner, no bias), GEGLU, Dropout, Linear(inner, d, no bias)).
     run(): LN -> GEMM with interleaved (value, gate) rows + GEGLU epilogue -> GEMM + residual."""
 
+    def _w1_interleaved(self, dtype):
+        """((2 * ip, d) f32 W1 with its (value, gate) rows interleaved for the GEGLU epilogue, ip = the inner width padded to that epilogue's vector)"""
+        lin1, lin2 = self[1], self[4]
+        inner = lin2.weight.shape[1]
+        ip = round_up(inner, 8 if dtype == L.BF16 else 4)
+        w1 = lin1.weight.detach().float()
+        w1p = torch.zeros((2 * ip, w1.shape[1]), device=w1.device, dtype=torch.float32)
+        w1p[0:2 * inner:2] = w1[:inner]          # value rows  (x, gate = chunk(2))
+        w1p[1:2 * inner:2] = w1[inner:]          # gate rows
+        return w1p, ip
+
     def _packed(self, dtype):
         lin1, lin2 = self[1], self[4]
 
         def build():
+            w1p, ip = self._w1_interleaved(dtype)
             inner = lin2.weight.shape[1]
-            q = 8 if dtype == L.BF16 else 4
-            ip = round_up(inner, q)
-            w1 = lin1.weight.detach()
-            d = w1.shape[1]
-            w1p = torch.zeros((2 * ip, d), device=w1.device, dtype=torch.float32)
-            w1p[0:2 * inner:2] = w1[:inner]          # value rows  (x, gate = chunk(2))
-            w1p[1:2 * inner:2] = w1[inner:]          # gate rows
-            w2p = torch.zeros((lin2.weight.shape[0], ip), device=w1.device, dtype=torch.float32)
+            w2p = torch.zeros((lin2.weight.shape[0], ip), device=w1p.device, dtype=torch.float32)
             w2p[:, :inner] = lin2.weight.detach()
             return pack_linear_weight(w1p, dtype), pack_linear_weight(w2p, dtype), ip
         return _cache(self).get(('ff', dtype), [lin1.weight, lin2.weight], build)
 
     def _packed_folded(self, dtype):
         """first GEMM with the block's nn.LayerNorm folded in: (gamma (.) W1 interleaved / padded, s, t, beta_is_zero)"""
-        lin1, lin2, ln = self[1], self[4], self[0]
+        lin1, ln = self[1], self[0]
+        return folded_weight(self, 'ff1_ln', lambda: self._w1_interleaved(dtype)[0], ln.weight, ln.bias, dtype, [lin1.weight, ln.weight, ln.bias])
 
-        def w1():
-            inner = lin2.weight.shape[1]
-            ip = round_up(inner, 8 if dtype == L.BF16 else 4)
-            w = lin1.weight.detach().float()
-            w1p = torch.zeros((2 * ip, w.shape[1]), device=w.device, dtype=torch.float32)
-            w1p[0:2 * inner:2] = w[:inner]
-            w1p[1:2 * inner:2] = w[inner:]
-            return w1p
-        return folded_weight(self, 'ff1_ln', w1, ln.weight, ln.bias, dtype, [lin1.weight, ln.weight, ln.bias])
-
-    def run(self, x2d, dtype, xt=None, want_t=False, stats=None):
-        """x2d (M, D) f32 -> ff(x) + x  (M, D) f32.  xt: the T copy of x2d (bf16 mode, LayerNorm folded into the first GEMM);
-        stats: the (M, D/32, 2) row statistics of xt its producer left (else the GEMM takes them from its own main loop);
-        want_t: also return the T copy of the result for the next block -> (out, out_t)."""
+    def _run(self, x2d, dtype, xt=None, want_t=False, stats=None):
+        """run() for Transformer.run: always (out, out_t or None, None), the one shape every block hands the next"""
         M, D = x2d.shape
         w1p, w2p, ip = self._packed(dtype)
         td = L.tdtype(dtype)
@@ -292,7 +286,14 @@ class FeedForwardSeq(nn.Sequential):
         out = torch.empty_like(x2d)
         out_t = torch.empty((M, D), device=x2d.device, dtype=td) if (want_t and dtype == L.BF16) else None
         L.gemm(dtype, hmid, w2p, M, D, ip, C=out, res=x2d, C2=out_t)
-        return (out, out_t) if want_t else out
+        return out, out_t, None
+
+    def run(self, x2d, dtype, xt=None, want_t=False, stats=None):
+        """x2d (M, D) f32 -> ff(x) + x  (M, D) f32.  xt: the T copy of x2d (bf16 mode, LayerNorm folded into the first GEMM);
+        stats: the (M, D/32, 2) row statistics of xt its producer left (else the GEMM takes them from its own main loop);
+        want_t: also return the T copy of the result for the next block -> (out, out_t)."""
+        r = self._run(x2d, dtype, xt, want_t, stats)
+        return r[:2] if want_t else r[0]
 
     def forward(self, x):
         L.require_device(x, 'x')
@@ -323,15 +324,20 @@ class PEG(PackedModule):
         w = self.dsconv.weight
         return _cache(self).get('wt', [w], lambda: w.detach().float().reshape(w.shape[0], 27).t().contiguous())
 
-    def run(self, x2d, shape, want_t=False):
-        """x2d (M, D) f32 contiguous, shape (b,t,h,w) with b*t*h*w == M -> peg(x) + x  [, its bf16 copy]"""
+    def _run(self, x2d, shape, want_t=False):
+        """run() for Transformer.run: always (out, out_t or None, None)"""
         b, t, h, w = shape
         M, D = x2d.shape
         assert b * t * h * w == M, 'PEG shape does not match the token buffer'
         out = torch.empty_like(x2d)
         out_t = torch.empty((M, D), device=x2d.device, dtype=torch.bfloat16) if want_t else None
         L.peg(x2d, self._packed(), self.dsconv.bias, out, b, t, h, w, D, self.causal, out_t=out_t)
-        return (out, out_t) if want_t else out
+        return out, out_t, None
+
+    def run(self, x2d, shape, want_t=False):
+        """x2d (M, D) f32 contiguous, shape (b,t,h,w) with b*t*h*w == M -> peg(x) + x  [, its bf16 copy]"""
+        r = self._run(x2d, shape, want_t)
+        return r[:2] if want_t else r[0]
 
     def forward(self, x, shape=None):
         L.require_device(x, 'x')
@@ -511,9 +517,10 @@ class Attention(PackedModule):
         return kv
 
     def _finish(self, o, x2d, dtype, want_t, dup=1):
-        """to_out projection + residual  [+ the bf16 copy of the result for the next block's folded LayerNorm; want_t == 'stats': and
-        the row statistics of that copy for a folded feed-forward LayerNorm -> (out, out_t, stats)].  dup = 2: the result (and its bf16
-        copy) is written twice, rows [0, M) and [M, 2M) -- the cond | null copies of a CFG batch that was identical up to here."""
+        """to_out projection + residual -> (out, out_t, stats): out_t the bf16 copy of the result for the next block's folded LayerNorm
+        (want_t, bf16 mode; else None), stats the row statistics of that copy for a folded feed-forward LayerNorm (want_t == 'stats';
+        else None).  dup = 2: the result (and its bf16 copy) is written twice, rows [0, M) and [M, 2M) -- the cond | null copies of a
+        CFG batch that was identical up to here."""
         M, D = x2d.shape
         out = torch.empty((dup * M, D), device=x2d.device, dtype=torch.float32)
         out_t = torch.empty((dup * M, D), device=x2d.device, dtype=torch.bfloat16) if (want_t and dtype == L.BF16) else None
@@ -523,9 +530,7 @@ class Attention(PackedModule):
             stats = torch.empty((M, (D + 31) // 32, 2), device=x2d.device, dtype=torch.float32)
         L.gemm(dtype, o, linear_weight(self.to_out, dtype), M, D, o.shape[1], C=out, res=x2d, C2=out_t, stats_out=stats,
                dup_rows=M if dup == 2 else 0)
-        if want_t == 'stats':
-            return out, out_t, stats
-        return (out, out_t) if want_t else out
+        return out, out_t, stats
 
     def _folded_q(self, dtype):
         """to_q with this block's LayerNorm folded in (gamma (.) Wq, s, t); None when the (zero) beta buffer is not zero"""
@@ -533,20 +538,10 @@ class Attention(PackedModule):
                                             [self.to_q.weight, self.norm.gamma, self.norm.beta])
         return (wg, s, t) if beta_zero else None
 
-    def run(self, x2d, S, n, dtype, *, context2d=None, n_ctx=None, attn_bias=None, kmask=None, kv_cache=None, xt=None, want_t=False, dup=1):
-        """x2d (S*n, D) f32 -> attention(x) + x.  kmask: (S, n_kv) uint8/bool over the real keys or None.
-        xt: the bf16 copy of x2d its producer wrote (bf16 mode: the block's LayerNorm is folded into to_q, K / V read the same
-        un-normalised rows); want_t: return (out, bf16 copy of out).  dup = 2: the outputs hold the result twice (see _finish)."""
-        dev = x2d.device
-        td = L.tdtype(dtype)
-        M, D = x2d.shape
-        h = self.heads
-        inner = self.to_q.weight.shape[0]
+    def _bias_form(self, attn_bias, dtype, n, is_cross, kmask):
+        """the form in which this call's position bias reaches the attention kernel -> (attn_bias (heads, n, n) or None, bias_table or
+        None, score_bound or None)"""
         nnull = self.num_null_kv
-        is_cross = context2d is not None
-        n_kv = n_ctx if is_cross else n
-        slopes = self.rel_pos_bias.slopes if self.causal else None
-        cached = kv_cache.get(id(self)) if (kv_cache is not None and is_cross) else None
         # a position bias given as a BiasSpec reaches the bf16 LDS attention kernel (n >= 64 keys and queries, no null keys / mask /
         # causal) as a 15 KB relative-position table instead of the (heads, n, n) matrix; every other consumer takes the matrix
         bias_table = None
@@ -569,109 +564,112 @@ class Attention(PackedModule):
                 score_bound = qk + hi
         if dtype == L.BF16X3 and bias_table is not None and score_bound is None:
             bias_table, attn_bias = None, spec.full            # no single exponent offset covers the range: the matrix form on the running-max kernel
+        return attn_bias, bias_table, score_bound
 
+    def _run(self, x2d, S, n, dtype, *, context2d=None, n_ctx=None, attn_bias=None, kmask=None, kv_cache=None, xt=None, want_t=False, dup=1):
+        """run() for Transformer.run: always (out, out_t or None, stats or None), see _finish"""
+        dev = x2d.device
+        td = L.tdtype(dtype)
+        M, D = x2d.shape
+        h = self.heads
+        inner = self.to_q.weight.shape[0]
+        nnull = self.num_null_kv
+        is_cross = context2d is not None
+        n_kv = n_ctx if is_cross else n
+        slopes = self.rel_pos_bias.slopes if self.causal else None
+        cached = kv_cache.get(id(self)) if (kv_cache is not None and is_cross) else None
+        attn_bias, bias_table, score_bound = self._bias_form(attn_bias, dtype, n, is_cross, kmask)
+        plain_self = not is_cross and nnull == 0              # what the fused projection kernels take besides a cached context
+
+        # ---- the operands: the rows to_q reads (xq), the rows K / V read (xkv), the to_q image, and which kernels exist for them
         fq = self._folded_q(dtype) if ln_fold_enabled(dtype) else None
-        if fq is not None:
-            # ---- bf16, LayerNorm folded: q = l2norm(x (gamma.Wq)^T - mean(x) s)  (the l2norm cancels rstd), K / V from the same x
+        folded = fq is not None
+        if folded:
+            # bf16 / split-bf16, LayerNorm folded: q = l2norm(x (gamma.Wq)^T - mean(x) s)  (the l2norm cancels rstd), K / V from the same x
             wq, sq, tq = fq
+            ln_q = (sq, tq, self.norm.eps)
             if xt is None:
                 xt = x2d.to(td)
-            if not is_cross and nnull == 0 and _SHORT_FUSED and n <= 64 and kmask is None and (attn_bias is None or attn_bias.stride(-1) == 1):
-                # short sequences (C-ViViT spatial n = 64 / temporal n = 9..10): projections + attention in ONE launch
-                o = torch.empty((M, inner), device=dev, dtype=td)
-                L.qkv_attn(xt, xt, wq, linear_weight(self.to_kv, dtype), S, n, h, D, self.q_scale, self.k_scale, float(self.scale), o,
-                           bias=attn_bias, slopes=slopes, causal=self.causal, q_ln_s=sq)
-                return self._finish(o, x2d, dtype, want_t, dup)
-            nq_pad, nk_pad = L.attn_pads(n, n_kv, nnull)
-            Qp = torch.empty((S * h * nq_pad * 64,), device=dev, dtype=td)
-            if not is_cross and nnull == 0:
-                Kp = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
-                Vt = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)      # pad columns: masked inside the attention kernels
-                L.qkv_project(xt, xt, wq, linear_weight(self.to_kv, dtype), S, n, h, D, self.q_scale, self.k_scale, float(self.scale),
-                              Qp, Kp, Vt, nq_pad, nk_pad, q_ln_s=sq)
-            elif cached is not None:
-                Kp, Vt = cached                       # step-invariant context: only the query side is projected again
-                if _CROSS_FUSED and n % 64 == 0 and nnull + n_kv <= 64:
-                    # few keys (the text context): query projection + attention against the cached images in ONE launch
-                    o = torch.empty((M, inner), device=dev, dtype=td)
-                    L.q_attn_cached(xt, wq, S, n, h, D, self.q_scale, float(self.scale), Kp, Vt, nk_pad, n_kv, nnull, o, kmask=kmask, q_ln_s=sq)
-                    return self._finish(o, x2d, dtype, want_t, dup)
-                L.qkv_project(xt, None, wq, None, S, n, h, D, self.q_scale, None, float(self.scale), Qp, None, None, nq_pad, nk_pad, q_ln_s=sq)
-            else:
-                q = torch.empty((M, inner), device=dev, dtype=torch.float32)
-                L.gemm(dtype, xt, wq, M, inner, D, C=q, ln=(sq, tq, self.norm.eps))
-                kv = self.project_kv(context2d if is_cross else xt, S, n_kv, dtype, is_cross)
-                Kp = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
-                Vt = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
-                L.attn_prep(dtype, q, kv, self.null_kv, self.q_scale, self.k_scale, float(self.scale), Qp, Kp, Vt, S, h, n, n_kv, nnull)
-                if kv_cache is not None and is_cross:
-                    kv_cache[id(self)] = (Kp, Vt)
+            xq = xt
+            xkv = context2d if is_cross else xt
+            small = False
+            projects = True
+        else:
+            # separate LayerNorm launch (exact-f32 mode; bf16 with PK_LN_FOLD=0; a non-zero beta)
+            wq, sq, ln_q = linear_weight(self.to_q, dtype), None, None
+            xq = torch.empty((M, D), device=dev, dtype=td)
+            # self-attention K/V come from the UN-normalised x (attention.py:140-144): in bf16 mode the same LN launch
+            # also emits x in bf16 so every GEMM operand is T and can be fed by LDS-DMA
+            xraw = torch.empty((M, D), device=dev, dtype=td) if (not is_cross and dtype == L.BF16) else None
+            L.layernorm(x2d, self.norm.gamma, self.norm.beta, M, D, out=xq, raw=xraw)
+            xkv = context2d if is_cross else (xraw if xraw is not None else x2d)
+            # exact-f32 mode, very short sequences: one fused f32 launch; in bf16 mode the fused projection + MFMA attention
+            # measured faster for the temporal layers (1.030 vs 1.046 ms per encode step)
+            small = plain_self and n <= 16 and dtype != L.BF16
+            projects = dtype == L.BF16
+        # to_q / to_kv run as ONE launch whose epilogue writes the attention operand images directly (pk_qkv_project, or with the
+        # attention behind it pk_qkv_attn / pk_q_attn_cached); available for self-attention (no null keys) and for cross-attention with
+        # cached K / V -- from bf16 rows, and from the f32 rows of the split-bf16 mode when the LayerNorm is folded
+        fused = projects and (plain_self or cached is not None)
+
+        # ---- the ladder
+        if (fused and plain_self and _SHORT_FUSED and n <= 64 and kmask is None and (attn_bias is None or attn_bias.stride(-1) == 1)):
+            # short sequences (C-ViViT spatial n = 64 / temporal n = 9..10): projections + attention in ONE launch
             o = torch.empty((M, inner), device=dev, dtype=td)
-            L.attn_fwd(dtype, Qp, Kp, Vt, o, S, h, n, n_kv, nnull, bias=attn_bias, kmask=kmask, slopes=slopes, causal=self.causal,
-                       bias_table=bias_table, score_bound=score_bound)
+            L.qkv_attn(xq, xkv, wq, linear_weight(self.to_kv, dtype), S, n, h, D, self.q_scale, self.k_scale, float(self.scale), o,
+                       bias=attn_bias, slopes=slopes, causal=self.causal, q_ln_s=sq)
             return self._finish(o, x2d, dtype, want_t, dup)
-
-        # ---- separate LayerNorm launch (exact-f32 mode; bf16 with PK_LN_FOLD=0)
-        xn = torch.empty((M, D), device=dev, dtype=td)
-        # self-attention K/V come from the UN-normalised x (attention.py:140-144): in bf16 mode the same LN launch
-        # also emits x in bf16 so every GEMM operand is T and can be fed by LDS-DMA
-        xraw = torch.empty((M, D), device=dev, dtype=td) if (not is_cross and dtype == L.BF16) else None
-        L.layernorm(x2d, self.norm.gamma, self.norm.beta, M, D, out=xn, raw=xraw)
-        # exact-f32 mode, very short sequences: one fused f32 launch; in bf16 mode the fused projection + MFMA attention
-        # measured faster for the temporal layers (1.030 vs 1.046 ms per encode step)
-        small = not is_cross and nnull == 0 and n <= 16 and dtype != L.BF16
-        # bf16: to_q / to_kv run as ONE GEMM launch whose epilogue writes the attention operand images directly
-        # (pk_qkv_project); available for self-attention (no null keys) and for cross-attention with cached K / V
-        fused = dtype == L.BF16 and not small and ((not is_cross and nnull == 0) or cached is not None)
-
-        if _SHORT_FUSED and fused and not is_cross and n <= 64 and kmask is None and (attn_bias is None or attn_bias.stride(-1) == 1):
-            o = torch.empty((M, inner), device=dev, dtype=td)
-            L.qkv_attn(xn, xraw, linear_weight(self.to_q, dtype), linear_weight(self.to_kv, dtype), S, n, h, D, self.q_scale,
-                       self.k_scale, float(self.scale), o, bias=attn_bias, slopes=slopes, causal=self.causal)
-            return self._finish(o, x2d, dtype, want_t, dup)
-
         q = None
         if not fused:
             q = torch.empty((M, inner), device=dev, dtype=torch.float32)
-            L.gemm(dtype, xn, linear_weight(self.to_q, dtype), M, inner, D, C=q)
-
+            L.gemm(dtype, xq, wq, M, inner, D, C=q, ln=ln_q)
         if small:
             # very short sequences (C-ViViT temporal layers, n = 9..10): l2norm, scales, ALiBi, softmax and PV in ONE
             # launch straight from the projection outputs (measured: 21 us vs 26 us for prep + MFMA attention; at n = 64
             # the f32 VALU loop loses to the MFMA path, 59 us vs 25 us, so the spatial layers keep that)
-            kv = self.project_kv(xraw if xraw is not None else x2d, S, n_kv, dtype, False)
+            kv = self.project_kv(xkv, S, n_kv, dtype, False)
             o = torch.empty((M, inner), device=dev, dtype=td)
             L.attn_small(q, kv, self.q_scale, self.k_scale, float(self.scale), o, S, h, n, bias=attn_bias, kmask=kmask,
                          slopes=slopes, causal=self.causal)
             return self._finish(o, x2d, dtype, want_t, dup)
-
         nq_pad, nk_pad = L.attn_pads(n, n_kv, nnull)
+        if folded and cached is not None and _CROSS_FUSED and n % 64 == 0 and nnull + n_kv <= 64:
+            # few keys (the text context): query projection + attention against the cached images in ONE launch (folded LayerNorm only)
+            o = torch.empty((M, inner), device=dev, dtype=td)
+            L.q_attn_cached(xq, wq, S, n, h, D, self.q_scale, float(self.scale), cached[0], cached[1], nk_pad, n_kv, nnull, o, kmask=kmask, q_ln_s=sq)
+            return self._finish(o, x2d, dtype, want_t, dup)
         Qp = torch.empty((S * h * nq_pad * 64,), device=dev, dtype=td)
-        if fused:
-            if is_cross:
-                Kp, Vt = cached
-                L.qkv_project(xn, None, linear_weight(self.to_q, dtype), None, S, n, h, D, self.q_scale, None, float(self.scale),
-                              Qp, None, None, nq_pad, nk_pad)
-            else:
-                Kp = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
-                # V^T pad columns (keys >= n) are never written: the attention kernels mask them in the tail tile
-                Vt = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
-                L.qkv_project(xn, xraw, linear_weight(self.to_q, dtype), linear_weight(self.to_kv, dtype), S, n, h, D,
-                              self.q_scale, self.k_scale, float(self.scale), Qp, Kp, Vt, nq_pad, nk_pad)
-        elif cached is None:
-            kv = self.project_kv(context2d if is_cross else (xraw if xraw is not None else x2d), S, n_kv, dtype, is_cross)
+        fill = cached is None                         # K^ / V^T are written by this call; else they are the step-invariant context images
+        if fill:                                      # of the kv_cache and only the query side is projected / prepared again
             Kp = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
+            # V^T pad columns (keys >= n) are never written: the attention kernels mask them in the tail tile
             Vt = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
-            L.attn_prep(dtype, q, kv, self.null_kv, self.q_scale, self.k_scale, float(self.scale), Qp, Kp, Vt, S, h, n, n_kv, nnull)
-            if kv_cache is not None and is_cross:
-                kv_cache[id(self)] = (Kp, Vt)
         else:
-            Kp, Vt = cached      # step-invariant context: only the query side is prepared again
-            L.attn_prep(dtype, q, None, self.null_kv, self.q_scale, self.k_scale, float(self.scale), Qp, None, None, S, h, n, n_kv, nnull)
+            Kp, Vt = cached
+        if fused and fill:
+            L.qkv_project(xq, xkv, wq, linear_weight(self.to_kv, dtype), S, n, h, D, self.q_scale, self.k_scale, float(self.scale),
+                          Qp, Kp, Vt, nq_pad, nk_pad, q_ln_s=sq)
+        elif fused:
+            L.qkv_project(xq, None, wq, None, S, n, h, D, self.q_scale, None, float(self.scale), Qp, None, None, nq_pad, nk_pad, q_ln_s=sq)
+        else:
+            kv = self.project_kv(xkv, S, n_kv, dtype, is_cross) if fill else None
+            L.attn_prep(dtype, q, kv, self.null_kv, self.q_scale, self.k_scale, float(self.scale), Qp, Kp if fill else None,
+                        Vt if fill else None, S, h, n, n_kv, nnull)
+            if fill and kv_cache is not None and is_cross:
+                kv_cache[id(self)] = (Kp, Vt)
         o = torch.empty((M, inner), device=dev, dtype=td)
         L.attn_fwd(dtype, Qp, Kp, Vt, o, S, h, n, n_kv, nnull, bias=attn_bias, kmask=kmask, slopes=slopes, causal=self.causal,
                    bias_table=bias_table, score_bound=score_bound)
         return self._finish(o, x2d, dtype, want_t, dup)
+
+    def run(self, x2d, S, n, dtype, *, context2d=None, n_ctx=None, attn_bias=None, kmask=None, kv_cache=None, xt=None, want_t=False, dup=1):
+        """x2d (S*n, D) f32 -> attention(x) + x.  kmask: (S, n_kv) uint8/bool over the real keys or None.
+        xt: the bf16 copy of x2d its producer wrote (bf16 mode: the block's LayerNorm is folded into to_q, K / V read the same
+        un-normalised rows); want_t: return (out, bf16 copy of out), want_t == 'stats': (out, bf16 copy, its row statistics).
+        dup = 2: the outputs hold the result twice (see _finish)."""
+        r = self._run(x2d, S, n, dtype, context2d=context2d, n_ctx=n_ctx, attn_bias=attn_bias, kmask=kmask, kv_cache=kv_cache, xt=xt,
+                      want_t=want_t, dup=dup)
+        return r if want_t == 'stats' else r[:2] if want_t else r[0]
 
     def forward(self, x, mask=None, context=None, attn_bias=None):
         L.require_device(x, 'x')
@@ -687,11 +685,7 @@ class Attention(PackedModule):
         return (out - x2).reshape(x.shape)
 
 
-def _unpack(r):
-    """out | (out, out_t) | (out, out_t, stats) -> (out, out_t, stats)"""
-    if not isinstance(r, tuple):
-        return r, None, None
-    return r if len(r) == 3 else (r[0], r[1], None)
+_FF_WANTS = (False, True, 'stats')          # ff_fold_mode -> the want_t of the block in front of the feed-forward
 
 
 class Transformer(PackedModule):
@@ -733,31 +727,24 @@ class Transformer(PackedModule):
         nl = len(self.layers)
         assert replicas == 1 or self.shares_cfg_prefix(dtype, context2d, self_attn_mask), 'replicas: see shares_cfg_prefix'
         S_cur = S // replicas
+        # a block whose LayerNorm is folded into its first GEMM reads the bf16 copy (xt) of the residual stream, which the block BEFORE it
+        # writes beside the f32 one (only when somebody will read it); with separate LayerNorm launches nobody does: no xt, no want_t
+        if not fold:
+            xt = None
+        ff_wants = _FF_WANTS[ff_fold_mode(S * n)] if fold else False          # what the block in front of the FF leaves for it
         for li, (peg, self_attn, cross_attn, ff) in enumerate(self.layers):
-            if fold:
-                # bf16: a block whose LayerNorm is folded into its first GEMM reads the bf16 copy (xt) of the residual stream, which the
-                # block BEFORE it writes beside the f32 one (only when somebody will read it)
-                has_cross = exists(cross_attn) and exists(context2d)
-                if exists(peg):
-                    x, xt = _unpack(peg.run(x, video_shape if S_cur == S else (video_shape[0] * S_cur // S, *video_shape[1:]),
-                                            want_t=dtype == L.BF16))[:2]           # (split-bf16 reads the f32 rows: no copy)
-                ff_wants = {0: False, 1: True, 2: 'stats'}[ff_fold_mode(S * n)]           # what the block in front of the FF leaves for it
-                x, xt, stats = _unpack(self_attn.run(x, S_cur, n, dtype, attn_bias=attn_bias, kmask=self_attn_mask, xt=xt,
-                                                     want_t=True if has_cross else ff_wants, dup=S // S_cur))
-                S_cur = S
-                if has_cross:
-                    x, xt, stats = _unpack(cross_attn.run(x, S, n, dtype, context2d=context2d, n_ctx=n_ctx, kmask=cross_attn_context_mask,
-                                                          kv_cache=kv_cache, xt=xt, want_t=ff_wants))
-                next_reads_xt = li + 1 < nl and not exists(self.layers[li + 1][0])       # next layer starts with attention (no PEG)
-                x, xt, _ = _unpack(ff.run(x, dtype, xt=xt, want_t=next_reads_xt, stats=stats))
-                continue
+            has_cross = exists(cross_attn) and exists(context2d)
             if exists(peg):
-                x = peg.run(x, video_shape)
-            x = self_attn.run(x, S, n, dtype, attn_bias=attn_bias, kmask=self_attn_mask)
-            if exists(cross_attn) and exists(context2d):
-                x = cross_attn.run(x, S, n, dtype, context2d=context2d, n_ctx=n_ctx, kmask=cross_attn_context_mask,
-                                   kv_cache=kv_cache)
-            x = ff.run(x, dtype)
+                x, xt, _ = peg._run(x, video_shape if S_cur == S else (video_shape[0] * S_cur // S, *video_shape[1:]),
+                                    want_t=fold and dtype == L.BF16)              # (split-bf16 reads the f32 rows: no copy)
+            x, xt, stats = self_attn._run(x, S_cur, n, dtype, attn_bias=attn_bias, kmask=self_attn_mask, xt=xt,
+                                          want_t=fold if has_cross else ff_wants, dup=S // S_cur)
+            S_cur = S
+            if has_cross:
+                x, xt, stats = cross_attn._run(x, S, n, dtype, context2d=context2d, n_ctx=n_ctx, kmask=cross_attn_context_mask,
+                                               kv_cache=kv_cache, xt=xt, want_t=ff_wants)
+            next_reads_xt = fold and li + 1 < nl and not exists(self.layers[li + 1][0])       # next layer starts with attention (no PEG)
+            x, xt, _ = ff._run(x, dtype, xt=xt, want_t=next_reads_xt, stats=stats)
         if skip_norm_out:
             return x
         if out is None and out_t is None:
