@@ -211,12 +211,19 @@ int pk_embed(const long long* ids_prime, int n_prime, const long long* ids, int 
 int pk_cpb_input(const float* w0, const float* b0, float* out, int d0, int d1, int d2, int nd, int D, void* stream);
 
 /* attention.py:146-157: head split, null-kv prepend, l2norm (k after the concat), q/k scales, sim scale folded in q;
- * writes Qp [S][h][nq_pad][64], Kp [S][h][nk_pad][64], Vt [S][h][64][nk_pad] in T. pk_attn_pads gives the pads.
- * kv == NULL prepares the query side only (cross-attention K/V cached across sampling steps). */
+ * writes Qp [S][h][nq_pad][dh], Kp [S][h][nk_pad][dh], Vt [S][h][dh][nk_pad] in T (dh = dim_head; 64 for pk_attn_prep), i.e.
+ * S*h*nq_pad*dh and twice S*h*nk_pad*dh elements. pk_attn_pads gives the pads (they do not depend on dim_head).
+ * kv == NULL prepares the query side only (cross-attention K/V cached across sampling steps).
+ * pk_attn_prep_dh: the same for dim_head = 32 | 64 | 128 (any other width: PK_EINVAL); q / kv hold h heads of dim_head columns, null_kv is
+ * [h][2*nnull][dim_head], q_scale / k_scale [dim_head].  dtype 2 images keep their 128-byte blocks of 32 elements (a row is dim_head / 32
+ * blocks), the bases sit on a 128-byte boundary.  pk_attn_prep is pk_attn_prep_dh(64, ...). */
 int pk_attn_pads(int nq, int n_kv, int nnull, int* nq_pad, int* nk_pad);
 int pk_attn_prep(int dtype, const float* q, int ldq, const float* kv, int ldkv, const float* null_kv,
                  const float* q_scale, const float* k_scale, float scale, void* Qp, void* Kp, void* Vt,
                  int S, int h, int nq, int n_kv, int nnull, void* stream);
+int pk_attn_prep_dh(int dim_head, int dtype, const float* q, int ldq, const float* kv, int ldkv, const float* null_kv,
+                    const float* q_scale, const float* k_scale, float scale, void* Qp, void* Kp, void* Vt,
+                    int S, int h, int nq, int n_kv, int nnull, void* stream);
 
 /* attention.py:142-157 in ONE launch (dtype 1 = bf16: bf16 rows / weights / images; dtype 2 = split-bf16, round 4: f32 rows split in
  * registers, host-split weight planes as for pk_gemm, images written pre-split as for pk_attn_prep(dtype 2)): to_q (A = xq = LayerNorm(x)) and to_kv (A = xkv = the un-normalised x, or NULL
@@ -246,12 +253,19 @@ int pk_q_attn_cached(int dtype, const void* xq, int ld, const void* wq, int ldw,
                      const float* q_ln_s, const void* Kp, const void* Vt, int nk_pad, int n_kv, int nnull,
                      const unsigned char* kmask, void* O, int ldo, void* stream);
 
-/* attention.py:157-182: softmax(sim + bias (+ key mask, + ALiBi, causal)) @ v, heads merged: O[(s,i)][hh*64 + d].
- * bias[hh][i][j] is over the real (non-null) keys; kmask [S][n_kv] uint8 (1 = keep); slopes [h] with causal. */
+/* attention.py:157-182: softmax(sim + bias (+ key mask, + ALiBi, causal)) @ v, heads merged: O[(s,i)][hh*dh + d] (dh = 64 for pk_attn_fwd).
+ * bias[hh][i][j] is over the real (non-null) keys; kmask [S][n_kv] uint8 (1 = keep); slopes [h] with causal.
+ * pk_attn_fwd_dh / pk_attn_fwd_lse_dh: the same on the images of pk_attn_prep_dh(dim_head, ...), dim_head = 32 | 64 | 128 (else PK_EINVAL).
+ * 64 is pk_attn_fwd / pk_attn_fwd_lse.  32 and 128 always run on the LDS-free kernel: bias_tab, a finite score_bound or a dropout site
+ * is PK_EINVAL there (the LDS-staged kernels, the fused projection kernels and the backward kernels are built for 64). */
 int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
                 int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
                 int out_is_f32, int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len,
                 const int* pos_code, int code_off, int tab_run4, float score_bound, void* stream);
+int pk_attn_fwd_dh(int dim_head, int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
+                   int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
+                   int out_is_f32, int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len,
+                   const int* pos_code, int code_off, int tab_run4, float score_bound, void* stream);
 /* a dropout site of the training kernels (the dropout paragraph further down): stream (seed, offset), keep_thr in [1, 256], scale = 1 / (1 - keep_thr / 256).
  * Every entry point that takes one takes NULL for no dropout. */
 typedef struct pk_dropout { unsigned long long seed, offset; int keep_thr; float scale; } pk_dropout;
@@ -263,6 +277,9 @@ typedef struct pk_dropout { unsigned long long seed, offset; int keep_thr; float
 int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
                     int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
                     int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse, const pk_dropout* drop, void* stream);
+int pk_attn_fwd_lse_dh(int dim_head, int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
+                       int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
+                       int out_is_f32, int S, int h, int nq, int n_kv, int nnull, float* lse, const pk_dropout* drop, void* stream);
 /* score_bound: an upper bound of sim + bias over every (head, query, key), or NaN.  q^ and k^ are unit vectors times q_scale / k_scale,
  * so |sim| <= scale * max_d |q_scale_d k_scale_d| and the caller knows the maximum of its bias: with a finite bound (and no key
  * mask, not causal, bf16, >= 64 queries and keys) the softmax numerators are p = 2^(s log2(e) - ceil(bound log2(e))) -- no running

@@ -55,11 +55,14 @@ SIGNATURES = {
     'pk_cpb_input': [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     'pk_attn_pads': [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)],
     'pk_attn_prep': [_I, _P, _I, _P, _I, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    'pk_attn_prep_dh': [_I, _I, _P, _I, _P, _I, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'pk_qkv_project': [_I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _I, _P, _P],
     'pk_qkv_attn': [_I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _L, _I, _P, _I, _P, _I, _P, _P],
     'pk_q_attn_cached': [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P],
     'pk_attn_fwd': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P],
+    'pk_attn_fwd_dh': [_I, _I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P],
     'pk_attn_fwd_lse': [_I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    'pk_attn_fwd_lse_dh': [_I, _I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'pk_attn_small': [_P, _I, _P, _I, _P, _P, _F, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'pk_cfg_mix': [_P, _I, _I, _I, _I, _P, _I, _F, _I, _P, _I, _I, _I, _P],
     'pk_vocab_ntiles': [_I],
@@ -406,11 +409,12 @@ def attn_pads(nq, n_kv, nnull):
     return a.value, b.value
 
 
-def attn_prep(dtype, q, kv, null_kv, q_scale, k_scale, scale, Qp, Kp, Vt, S, h, nq, n_kv, nnull):
-    """q_scale = k_scale = None: plain dot-product attention operands (no l2norm; q * scale) -- the T5 text encoder"""
-    rc = load().pk_attn_prep(dtype, ptr(q), q.stride(-2), ptr(kv), kv.stride(-2) if kv is not None else 0, f32p(null_kv, 'null_kv') if nnull else None,
+def attn_prep(dtype, q, kv, null_kv, q_scale, k_scale, scale, Qp, Kp, Vt, S, h, nq, n_kv, nnull, dim_head=64):
+    """q_scale = k_scale = None: plain dot-product attention operands (no l2norm; q * scale) -- the T5 text encoder.
+    dim_head: 32 | 64 | 128, the width of a head in q / kv / null_kv / the scales and of the image rows"""
+    rc = load().pk_attn_prep_dh(dim_head, dtype, ptr(q), q.stride(-2), ptr(kv), kv.stride(-2) if kv is not None else 0, f32p(null_kv, 'null_kv') if nnull else None,
                              f32p(q_scale, 'q_scale'), f32p(k_scale, 'k_scale'), scale, ptr(Qp), ptr(Kp), ptr(Vt), S, h, nq, n_kv, nnull, stream(q))
-    _check(rc, 'pk_attn_prep')
+    _check(rc, 'pk_attn_prep_dh')
 
 
 def rmsnorm(x, w, M, D, out, eps=1e-6, rowmask=None):
@@ -457,10 +461,11 @@ def q_attn_cached(xq, wq, S, n, h, K, q_scale, scale, Kp, Vt, nk_pad, n_kv, nnul
 
 
 def attn_fwd(dtype, Qp, Kp, Vt, O, S, h, nq, n_kv, nnull, *, bias=None, kmask=None, slopes=None, causal=False, bias_table=None,
-             score_bound=None, lse=None, drop=None):
+             score_bound=None, lse=None, drop=None, dim_head=64):
     """bias: full (h, nq, n_kv) f32 tensor, or bias_table = (tab (h, L) f32, pos_code (n,) int32, offset, ...): the relative-position
     form.  score_bound: upper bound of sim + bias (python float) -> fixed-offset softmax; None: running-max flash loop.
-    lse ((S h nq,) f32; the training forward): also write every row's log-sum-exp for pk_attn_bwd_ws."""
+    lse ((S h nq,) f32; the training forward): also write every row's log-sum-exp for pk_attn_bwd_ws.
+    dim_head: 32 | 64 | 128 as given to attn_prep; other than 64: the LDS-free kernel, no bias_table / score_bound / drop."""
     tab, codes, off = bias_table[:3] if bias_table is not None else (None, None, 0)
     run4 = 1 if (bias_table is not None and len(bias_table) > 5 and bias_table[5]) else 0
     if bias is not None:
@@ -469,16 +474,16 @@ def attn_fwd(dtype, Qp, Kp, Vt, O, S, h, nq, n_kv, nnull, *, bias=None, kmask=No
         bh, bld = 0, 0
     if lse is not None or drop is not None:                               # the training forward; drop: the DropSite of attn_dropout > 0
         assert lse is not None and bias_table is None and score_bound is None
-        rc = load().pk_attn_fwd_lse(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
+        rc = load().pk_attn_fwd_lse_dh(dim_head, dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
                                     1 if causal else 0, ptr(O), O.stride(-2), 1 if O.dtype == torch.float32 else 0, S, h, nq, n_kv, nnull, ptr(lse),
                                     _site(drop), stream(O))
-        _check(rc, 'pk_attn_fwd_lse')
+        _check(rc, 'pk_attn_fwd_lse_dh')
         return
-    rc = load().pk_attn_fwd(dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
+    rc = load().pk_attn_fwd_dh(dim_head, dtype, ptr(Qp), ptr(Kp), ptr(Vt), ptr(bias), bh, bld, ptr(kmask), f32p(slopes, 'ALiBi slopes'),
                             1 if causal else 0, ptr(O), O.stride(-2), 1 if O.dtype == torch.float32 else 0,
                             S, h, nq, n_kv, nnull, f32p(tab, 'bias table'), tab.shape[1] if tab is not None else 0, ptr(codes), off, run4,
                             float('nan') if score_bound is None else float(score_bound), stream(O))
-    _check(rc, 'pk_attn_fwd')
+    _check(rc, 'pk_attn_fwd_dh')
 
 
 def attn_small(q, kv, q_scale, k_scale, scale, O, S, h, n, *, bias=None, kmask=None, slopes=None, causal=False):

@@ -474,13 +474,28 @@ _CFG_SHARED_PREFIX = os.environ.get('PK_CFG_SHARED_PREFIX', '1') != '0'
 _ATTN_FIXED = os.environ.get('PK_ATTN_FIXED', '1') != '0'
 
 
+DIM_HEADS = (32, 64, 128)               # head widths pk_attn_prep_dh / pk_attn_fwd_dh are built for
+
+
+def require_train_dim_head(*modules):
+    """the backward kernels (and the fused forward kernels a training step runs) are 64-wide: refuse a graph over any other width, before a launch"""
+    for m in modules:
+        for sub in (m.modules() if m is not None else ()):
+            if isinstance(sub, Attention) and sub.dim_head != 64:
+                raise NotImplementedError(f'training kernels exist for dim_head = 64 only, this module has dim_head = {sub.dim_head}: '
+                                          'widths 32 and 128 run inference only (torch.no_grad() / frozen parameters)')
+
+
 class Attention(PackedModule):
-    """attention.py:89-182."""
+    """attention.py:89-182.  dim_head 64: every kernel of the ladder in _run.  dim_head 32 / 128: the general route only (LayerNorm or its
+    folded form, q / kv GEMMs, pk_attn_prep_dh, the LDS-free pk_attn_fwd_dh, to_out), inference only."""
 
     def __init__(self, dim, dim_context=None, dim_head=64, heads=8, causal=False, num_null_kv=0,
                  norm_context=True, dropout=0., scale=8):
         super().__init__()
-        assert dim_head == 64, 'the MI355X attention kernels are built for dim_head = 64 (the reference default)'
+        if dim_head not in DIM_HEADS:
+            raise ValueError(f'dim_head = {dim_head}: the MI355X attention kernels are built for dim_head 32, 64 (the reference default) and 128')
+        self.dim_head = dim_head
         self.heads = heads
         self.causal = causal
         self.scale = scale
@@ -542,6 +557,8 @@ class Attention(PackedModule):
         """the form in which this call's position bias reaches the attention kernel -> (attn_bias (heads, n, n) or None, bias_table or
         None, score_bound or None)"""
         nnull = self.num_null_kv
+        if self.dim_head != 64:                                 # the table and the fixed-offset softmax live in the 64-wide LDS-staged kernel
+            return _full_bias(attn_bias), None, None
         # a position bias given as a BiasSpec reaches the bf16 LDS attention kernel (n >= 64 keys and queries, no null keys / mask /
         # causal) as a 15 KB relative-position table instead of the (heads, n, n) matrix; every other consumer takes the matrix
         bias_table = None
@@ -571,7 +588,9 @@ class Attention(PackedModule):
         dev = x2d.device
         td = L.tdtype(dtype)
         M, D = x2d.shape
-        h = self.heads
+        h, dh = self.heads, self.dim_head
+        if dh != 64 and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            require_train_dim_head(self)
         inner = self.to_q.weight.shape[0]
         nnull = self.num_null_kv
         is_cross = context2d is not None
@@ -611,6 +630,9 @@ class Attention(PackedModule):
         # attention behind it pk_qkv_attn / pk_q_attn_cached); available for self-attention (no null keys) and for cross-attention with
         # cached K / V -- from bf16 rows, and from the f32 rows of the split-bf16 mode when the LayerNorm is folded
         fused = projects and (plain_self or cached is not None)
+        if dh != 64:
+            # pk_qkv_attn / pk_qkv_project / pk_q_attn_cached / pk_attn_small are 64-wide: the general route below, whatever n is
+            fused = small = False
 
         # ---- the ladder
         if (fused and plain_self and _SHORT_FUSED and n <= 64 and kmask is None and (attn_bias is None or attn_bias.stride(-1) == 1)):
@@ -633,17 +655,17 @@ class Attention(PackedModule):
                          slopes=slopes, causal=self.causal)
             return self._finish(o, x2d, dtype, want_t, dup)
         nq_pad, nk_pad = L.attn_pads(n, n_kv, nnull)
-        if folded and cached is not None and _CROSS_FUSED and n % 64 == 0 and nnull + n_kv <= 64:
+        if folded and cached is not None and _CROSS_FUSED and dh == 64 and n % 64 == 0 and nnull + n_kv <= 64:
             # few keys (the text context): query projection + attention against the cached images in ONE launch (folded LayerNorm only)
             o = torch.empty((M, inner), device=dev, dtype=td)
             L.q_attn_cached(xq, wq, S, n, h, D, self.q_scale, float(self.scale), cached[0], cached[1], nk_pad, n_kv, nnull, o, kmask=kmask, q_ln_s=sq)
             return self._finish(o, x2d, dtype, want_t, dup)
-        Qp = torch.empty((S * h * nq_pad * 64,), device=dev, dtype=td)
+        Qp = torch.empty((S * h * nq_pad * dh,), device=dev, dtype=td)
         fill = cached is None                         # K^ / V^T are written by this call; else they are the step-invariant context images
         if fill:                                      # of the kv_cache and only the query side is projected / prepared again
-            Kp = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
+            Kp = torch.empty((S * h * nk_pad * dh,), device=dev, dtype=td)
             # V^T pad columns (keys >= n) are never written: the attention kernels mask them in the tail tile
-            Vt = torch.empty((S * h * nk_pad * 64,), device=dev, dtype=td)
+            Vt = torch.empty((S * h * nk_pad * dh,), device=dev, dtype=td)
         else:
             Kp, Vt = cached
         if fused and fill:
@@ -654,12 +676,12 @@ class Attention(PackedModule):
         else:
             kv = self.project_kv(xkv, S, n_kv, dtype, is_cross) if fill else None
             L.attn_prep(dtype, q, kv, self.null_kv, self.q_scale, self.k_scale, float(self.scale), Qp, Kp if fill else None,
-                        Vt if fill else None, S, h, n, n_kv, nnull)
+                        Vt if fill else None, S, h, n, n_kv, nnull, dim_head=dh)
             if fill and kv_cache is not None and is_cross:
                 kv_cache[id(self)] = (Kp, Vt)
         o = torch.empty((M, inner), device=dev, dtype=td)
         L.attn_fwd(dtype, Qp, Kp, Vt, o, S, h, n, n_kv, nnull, bias=attn_bias, kmask=kmask, slopes=slopes, causal=self.causal,
-                   bias_table=bias_table, score_bound=score_bound)
+                   bias_table=bias_table, score_bound=score_bound, dim_head=dh)
         return self._finish(o, x2d, dtype, want_t, dup)
 
     def run(self, x2d, S, n, dtype, *, context2d=None, n_ctx=None, attn_bias=None, kmask=None, kv_cache=None, xt=None, want_t=False, dup=1):

@@ -3,8 +3,8 @@
 //  pk_attn_prep : head split, null-kv prepend (interleaved k,v,k,v rows of `null_kv`, attention.py:148),
 //                 l2norm of q and of k AFTER the null-k concat (attention.py:153), * q_scale / k_scale,
 //                 * scale (8, attention.py:157, folded into q), V stored TRANSPOSED per head.
-//                 Layouts written (T = bf16 | f32):
-//                   Qp [S][h][nq_pad][64]   Kp [S][h][nk_pad][64]   Vt [S][h][64][nk_pad]
+//                 Layouts written (T = bf16 | f32; DH = dim_head):
+//                   Qp [S][h][nq_pad][DH]   Kp [S][h][nk_pad][DH]   Vt [S][h][DH][nk_pad]
 //                 nk = nnull + n_kv, pads are zero-filled.
 //  pk_attn_fwd  : softmax(Qp Kp^T + bias (+ALiBi, causal, key mask)) V, flash-style, LDS-free:
 //                 one wave owns 16*QF query rows; per 32-key tile it computes S^T = K Q^T and
@@ -12,38 +12,44 @@
 //                 lane-local up to a 4-lane-group shuffle, and P never leaves registers
 //                 (the S^T accumulator layout IS the P^T operand layout under the key permutation
 //                 key = (j >> 2)*16 + g*4 + (j & 3) that V^T's fragment loads use too).
-// dim_head is fixed at 64 (the reference default; every BASELINE config).
+// dim_head: these two kernels take the head width DH as a template parameter, 32 | 64 | 128 (pk_attn_prep_dh / pk_attn_fwd_dh; the
+// reference takes any width, attention.py:93-101); their DH = 64 instantiations are the kernels as they were.  Every other kernel of the
+// attention path -- the LDS-staged attn_fwd_lds_kernel with its bias table and fixed-offset softmax, pk_attn_small, the fused projection
+// kernels of qkv.hip / qkv_attn.hip, the backward kernels of attn_train.hip -- is built for 64 (DH64) and never sees another width: the
+// host sends a 32- or 128-wide module down the general ladder (q / kv GEMMs -> pk_attn_prep_dh -> attn_fwd_kernel) whatever n is.
 // Roofline: MFMA for n = 576 (4*nq*nk*64 flops per head), L1/L2 operand-fetch bound at small QF.
 #include <cstdlib>
 #include "common.hpp"
 
 namespace pk {
 
-constexpr int DH = 64;
+constexpr int DH64 = 64;                // the width of every kernel that is not templated on it
 
 struct PrepArgs {
-    const float* q; int ldq;        // [S*nq][ldq], head hh at columns hh*64
-    const float* kv; int ldkv;      // [S*n_kv][ldkv], k at columns [0, h*64), v at [h*64, 2*h*64)
-    const float* null_kv;           // [h][2*nnull][64] or null
-    const float* q_scale;           // [64]
-    const float* k_scale;           // [64]
+    const float* q; int ldq;        // [S*nq][ldq], head hh at columns hh*DH
+    const float* kv; int ldkv;      // [S*n_kv][ldkv], k at columns [0, h*DH), v at [h*DH, 2*h*DH)
+    const float* null_kv;           // [h][2*nnull][DH] or null
+    const float* q_scale;           // [DH]
+    const float* k_scale;           // [DH]
     void* Qp; void* Kp; void* Vt;
     int S, h, nq, n_kv, nnull, nq_pad, nk_pad;
     float scale;
 };
 
-// 16 lanes per (sequence, head, row): each lane owns 4 consecutive head dims (one 16-byte load), the row's
-// sum of squares is a 4-step xor-shuffle inside the 16-lane group.
-__device__ __forceinline__ float group16_sum(float v) {
+// LG = DH / 4 lanes per (sequence, head, row) -- 8, 16 or 32: each lane owns 4 consecutive head dims (one 16-byte load), the row's
+// sum of squares is a log2(LG)-step xor-shuffle inside the LG-lane group.
+template <int LG>
+__device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
+    for (int o = LG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LG);
     return v;
 }
 
-template <typename T>
+template <typename T, int DH>
 __device__ __forceinline__ void prep_q_block(const PrepArgs& p, long bid) {
-    const int l16 = threadIdx.x & 15;
-    const long r = bid * 16 + (threadIdx.x >> 4);                        // row index over (s, hh, i) incl. pad rows
+    constexpr int LG = DH / 4, ROWS = 256 / LG;                          // lanes per row, rows per block
+    const int l16 = threadIdx.x & (LG - 1);
+    const long r = bid * ROWS + (threadIdx.x / LG);                      // row index over (s, hh, i) incl. pad rows
     const long total = (long)p.S * p.h * p.nq_pad;
     if (r >= total) return;
     const int i = (int)(r % p.nq_pad);
@@ -53,7 +59,7 @@ __device__ __forceinline__ void prep_q_block(const PrepArgs& p, long bid) {
     if (i < p.nq) {
         const f32x4 x = *reinterpret_cast<const f32x4*>(p.q + ((size_t)s * p.nq + i) * p.ldq + hh * DH + l16 * 4);
         if (p.q_scale) {
-            const float ss = group16_sum((x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]));
+            const float ss = group_sum<LG>((x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]));
             const float inv = p.scale / fmaxf(sqrtf(ss), 1e-12f);               // F.normalize eps = 1e-12
             const f32x4 qs = *reinterpret_cast<const f32x4*>(p.q_scale + l16 * 4);
 #pragma unroll
@@ -66,10 +72,11 @@ __device__ __forceinline__ void prep_q_block(const PrepArgs& p, long bid) {
     store4(reinterpret_cast<T*>(p.Qp) + (size_t)r * DH + l16 * 4, v);
 }
 
-template <typename T>
-__device__ __forceinline__ void prep_kv_block(const PrepArgs& p, float (*vt)[65], int bid) {
-    // one block per (s, hh, 64-key tile); thread -> (key = tid >> 4 (+16 per pass), 4 head dims)
-    const int l16 = threadIdx.x & 15;
+template <typename T, int DH>
+__device__ __forceinline__ void prep_kv_block(const PrepArgs& p, float (*vt)[DH + 1], int bid) {
+    // one block per (s, hh, 64-key tile); thread -> (key = tid / LG (+ 256 / LG per pass), 4 head dims): tid >> 4, +16 at DH = 64
+    constexpr int LG = DH / 4, ROWS = 256 / LG;
+    const int l16 = threadIdx.x & (LG - 1);
     const int tiles = (p.nk_pad + 63) / 64;
     const int kt = bid % tiles;
     const int sh = bid / tiles;
@@ -79,7 +86,7 @@ __device__ __forceinline__ void prep_kv_block(const PrepArgs& p, float (*vt)[65]
     T* Vt = reinterpret_cast<T*>(p.Vt) + (size_t)sh * DH * p.nk_pad;
     const int kend = (p.nk_pad - kt * 64) < 64 ? (p.nk_pad - kt * 64) : 64;   // keys of this tile that exist in the padded image
     const f32x4 ks = p.k_scale ? *reinterpret_cast<const f32x4*>(p.k_scale + l16 * 4) : f32x4{1.f, 1.f, 1.f, 1.f};
-    for (int jj = threadIdx.x >> 4; jj < kend; jj += 16) {
+    for (int jj = threadIdx.x / LG; jj < kend; jj += ROWS) {         // kend % 32 == 0: whole waves enter or leave together
         const int key = kt * 64 + jj;
         f32x4 kx = f32x4{0, 0, 0, 0}, vx = kx;
         if (key < p.nnull) {
@@ -90,7 +97,7 @@ __device__ __forceinline__ void prep_kv_block(const PrepArgs& p, float (*vt)[65]
             kx = *reinterpret_cast<const f32x4*>(row + hh * DH + l16 * 4);
             vx = *reinterpret_cast<const f32x4*>(row + p.h * DH + hh * DH + l16 * 4);
         }
-        const float ss = group16_sum((kx[0] * kx[0] + kx[1] * kx[1]) + (kx[2] * kx[2] + kx[3] * kx[3]));
+        const float ss = group_sum<LG>((kx[0] * kx[0] + kx[1] * kx[1]) + (kx[2] * kx[2] + kx[3] * kx[3]));
         const float inv = key < nk ? (p.k_scale ? 1.0f / fmaxf(sqrtf(ss), 1e-12f) : 1.0f) : 0.f;      // k_scale == NULL: plain keys (T5)
         f32x4 kn;
 #pragma unroll
@@ -98,24 +105,29 @@ __device__ __forceinline__ void prep_kv_block(const PrepArgs& p, float (*vt)[65]
         store4(Kp + (size_t)key * DH + l16 * 4, kn);
     }
     __syncthreads();
-    // transposed store: thread -> (d = tid >> 2, 16 consecutive keys)
-    const int d = threadIdx.x >> 2, j0 = (threadIdx.x & 3) * 16;
+    // transposed store: slot -> (d = slot >> 2, 16 consecutive keys); 4 DH slots: half the block at DH = 32, one trip at 64, two at 128
 #pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-        const int jl = j0 + q4 * 4;
-        if (jl < kend) {   // nk_pad % 4 == 0
-            const f32x4 o = f32x4{vt[jl + 0][d], vt[jl + 1][d], vt[jl + 2][d], vt[jl + 3][d]};
-            store4(Vt + (size_t)d * p.nk_pad + kt * 64 + jl, o);
+    for (int trip = 0; trip < (4 * DH + 255) / 256; ++trip) {
+        const int slot = trip * 256 + threadIdx.x;
+        const int d = slot >> 2, j0 = (slot & 3) * 16;
+        if (4 * DH < 256 && slot >= 4 * DH) break;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int jl = j0 + q4 * 4;
+            if (jl < kend) {   // nk_pad % 4 == 0
+                const f32x4 o = f32x4{vt[jl + 0][d], vt[jl + 1][d], vt[jl + 2][d], vt[jl + 3][d]};
+                store4(Vt + (size_t)d * p.nk_pad + kt * 64 + jl, o);
+            }
         }
     }
 }
 
 // both operand-image kernels in ONE launch (round 6): blocks [0, nqb) lay down the Q^ image, the rest the K^ / V^T images
-template <typename T>
+template <typename T, int DH>
 __global__ __launch_bounds__(256) void prep_qkv_kernel(const PrepArgs p, int nqb) {
-    __shared__ float vt[64][65];
-    if ((int)blockIdx.x < nqb) prep_q_block<T>(p, blockIdx.x);
-    else prep_kv_block<T>(p, vt, (int)blockIdx.x - nqb);
+    __shared__ float vt[64][DH + 1];                        // the V transpose tile: 8.3 / 16.6 / 33 KB at DH = 32 / 64 / 128
+    if ((int)blockIdx.x < nqb) prep_q_block<T, DH>(p, blockIdx.x);
+    else prep_kv_block<T, DH>(p, vt, (int)blockIdx.x - nqb);
 }
 
 struct AttnArgs {
@@ -123,7 +135,7 @@ struct AttnArgs {
     const float* bias; long bias_hstride; int bias_ld;   // bias[hh][i][j] over REAL keys j, or null
     const unsigned char* kmask;                            // [S][n_kv] (1 = keep) over real keys, or null
     const float* slopes;                                   // ALiBi slopes [h] (causal layers), or null
-    void* O; int ldo; int out_f32;                         // O[(s*nq + i)][hh*64 + d]
+    void* O; int ldo; int out_f32;                         // O[(s*nq + i)][hh*DH + d]
     int S, h, nq, n_kv, nnull, nq_pad, nk_pad, causal;
     int bias_vec;                                          // bias rows are 16-byte loadable (nnull == 0, aligned strides)
     // relative-position bias as a TABLE (LDS-staged kernel only): bias[hh][i][j] = bias_tab[hh][pos_code[i] - pos_code[j] + code_off].
@@ -205,10 +217,12 @@ __device__ __forceinline__ void mask_vt_tail(Frag<float>& f, int kb, int g, int 
 // DROP (the training forward with attn_dropout > 0, attention.py:177): the softmax statistics (running max, row sum, lse) are those of the undropped
 // probabilities; the P that multiplies V is masked by the keep function (common.hpp) and the output scaled by 1 / (1 - p_eff).  A compile-time
 // flag: the DROP = false instantiation is the kernel as it was.
-template <typename T, int QF, bool DROP = false>
+// DH = dim_head (32 | 64 | 128): Q / K rows are NC = DH / 32 fragments, the output accumulators ND = DH / 16.
+template <typename T, int QF, bool DROP = false, int DH = 64>
 // QF = 2 on f32 / split-bf16 operands (the training step's n = 576 forward, the f32 / bf16x3 parity modes): the compiler's free choice was
 // ~250 VGPRs + 32 AGPRs = one wave per SIMD, 256 resident workgroups for the 320 of a B = 8 call; two waves per SIMD put them in one round
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 && sizeof(T) != 2) ? 2 : 1))) void attn_fwd_kernel(const AttnArgs p, const DropParam<DROP> dr) {
+    constexpr int NC = DH / 32, ND = DH / 16;
     const int lane = threadIdx.x & 63, g = lane >> 4, lr = lane & 15;
     const int qtiles = p.nq_pad / (16 * QF);
     const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -223,19 +237,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
     const T* Kp = reinterpret_cast<const T*>(p.Kp) + (size_t)sh * p.nk_pad * DH;
     const T* Vt = reinterpret_cast<const T*>(p.Vt) + (size_t)sh * DH * p.nk_pad;
 
-    Frag<T> fq[QF][2];
+    Frag<T> fq[QF][NC];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) frag_load(fq[qf][c], Qp + (size_t)(qf * 16 + lr) * DH + c * 32 + g * 8);
+        for (int c = 0; c < NC; ++c) frag_load(fq[qf][c], Qp + (size_t)(qf * 16 + lr) * DH + c * 32 + g * 8);
 
     float m[QF], l[QF];
-    f32x4 o[QF][4];
+    f32x4 o[QF][ND];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {
         m[qf] = -INFINITY; l[qf] = 0.f;
 #pragma unroll
-        for (int df = 0; df < 4; ++df) o[qf][df] = f32x4{0, 0, 0, 0};
+        for (int df = 0; df < ND; ++df) o[qf][df] = f32x4{0, 0, 0, 0};
     }
     const float slope = (p.causal && p.slopes) ? p.slopes[hh] : 0.f;
     const float* bias = p.bias ? p.bias + (size_t)hh * p.bias_hstride : nullptr;
@@ -254,11 +268,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
 #pragma unroll
         for (int qf = 0; qf < QF; ++qf) rowh[qf] = drop_row(dr, (uint32_t)sh * (uint32_t)p.nq + (uint32_t)(q0 + qf * 16 + lr));
     }
-    auto load_k = [&](Frag<T> (&fk)[2][2], int kb) {
+    auto load_k = [&](Frag<T> (&fk)[2][NC], int kb) {
 #pragma unroll
         for (int f = 0; f < 2; ++f)
 #pragma unroll
-            for (int c = 0; c < 2; ++c) frag_load(fk[f][c], Kp + (size_t)(kb + f * 16 + lr) * DH + c * 32 + g * 8);
+            for (int c = 0; c < NC; ++c) frag_load(fk[f][c], Kp + (size_t)(kb + f * 16 + lr) * DH + c * 32 + g * 8);
     };
     auto load_bias = [&](f32x4 (&bz)[QF][2], int kb) {
 #pragma unroll
@@ -267,20 +281,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
             for (int f = 0; f < 2; ++f)
                 bz[qf][f] = *reinterpret_cast<const f32x4*>(bias + (size_t)qrow[qf] * p.bias_ld + kb + f * 16 + g * 4);
     };
-    Frag<T> fk[2][2];
+    Frag<T> fk[2][NC];
     f32x4 bz[QF][2];
     load_k(fk, 0);
     if (vb_all && 32 <= nk) load_bias(bz, 0);
 
     for (int kb = 0; kb < p.nk_pad; kb += 32) {
-        Frag<T> fv[4];
+        Frag<T> fv[ND];
 #pragma unroll
-        for (int df = 0; df < 4; ++df) load_vt(fv[df], Vt + (size_t)(df * 16 + lr) * p.nk_pad, kb, g);
+        for (int df = 0; df < ND; ++df) load_vt(fv[df], Vt + (size_t)(df * 16 + lr) * p.nk_pad, kb, g);
         if (kb + 32 > nk) {                                   // wave-uniform: only the tail tile
 #pragma unroll
-            for (int df = 0; df < 4; ++df) mask_vt_tail(fv[df], kb, g, nk);
+            for (int df = 0; df < ND; ++df) mask_vt_tail(fv[df], kb, g, nk);
         }
-        Frag<T> fkn[2][2];
+        Frag<T> fkn[2][NC];
         f32x4 bzn[QF][2];
         const bool has_next = kb + 32 < p.nk_pad;
         if (has_next) {
@@ -293,7 +307,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
 #pragma unroll
         for (int f = 0; f < 2; ++f)
 #pragma unroll
-            for (int c = 0; c < 2; ++c)
+            for (int c = 0; c < NC; ++c)
 #pragma unroll
                 for (int qf = 0; qf < QF; ++qf) st[qf][f] = mma(fk[f][c], fq[qf][c], st[qf][f]);
         // whole-tile fast paths (wave-uniform): a full tile of real keys with no key mask / causal structure needs no
@@ -343,7 +357,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
             l[qf] = l[qf] * alpha + ls;
             m[qf] = mn;
 #pragma unroll
-            for (int df = 0; df < 4; ++df) o[qf][df] *= alpha;
+            for (int df = 0; df < ND; ++df) o[qf][df] *= alpha;
             if constexpr (DROP) {
                 // the lane's keys kb + f * 16 + g * 4 + 0..3 are one group of the keep function: one draw per block f
 #pragma unroll
@@ -359,14 +373,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
 #pragma unroll
         for (int qf = 0; qf < QF; ++qf) frag_from_f32(fp[qf], pr[qf]);
 #pragma unroll
-        for (int df = 0; df < 4; ++df)
+        for (int df = 0; df < ND; ++df)
 #pragma unroll
             for (int qf = 0; qf < QF; ++qf) o[qf][df] = mma(fv[df], fp[qf], o[qf][df]);
         if (has_next) {
 #pragma unroll
             for (int f = 0; f < 2; ++f)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) fk[f][c] = fkn[f][c];
+                for (int c = 0; c < NC; ++c) fk[f][c] = fkn[f][c];
 #pragma unroll
             for (int qf = 0; qf < QF; ++qf) { bz[qf][0] = bzn[qf][0]; bz[qf][1] = bzn[qf][1]; }
         }
@@ -383,7 +397,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QF == 2 &&
         const int qi = q0 + qf * 16 + lr;
         if (qi < p.nq) {
 #pragma unroll
-            for (int df = 0; df < 4; ++df) {
+            for (int df = 0; df < ND; ++df) {
                 const size_t off = ((size_t)s * p.nq + qi) * p.ldo + hh * DH + df * 16 + g * 4;
                 const f32x4 v = o[qf][df] * inv;
                 if (p.out_f32) store4(Of + off, v); else store4(Ot + off, v);
@@ -490,14 +504,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 
     // Q fragment rows are clamped to the head's image: with 48 rows per wave (QF = 3) the last wave of a head reaches past nq_pad whenever
     // nq_pad % 48 != 0 (n = 320: rows 320..335), i.e. into the next head's rows or, for the last (s, h), past the allocation
-    const T* Qp = reinterpret_cast<const T*>(p.Qp) + (size_t)sh * p.nq_pad * DH;
+    const T* Qp = reinterpret_cast<const T*>(p.Qp) + (size_t)sh * p.nq_pad * DH64;
     Frag<T> fq[QF][2];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {
         const int qr = active ? q0 + qf * 16 + lr : lr;
         const int qc = qr < p.nq_pad ? qr : p.nq_pad - 1;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) frag_load(fq[qf][c], Qp + (size_t)qc * DH + c * 32 + g * 8);
+        for (int c = 0; c < 2; ++c) frag_load(fq[qf][c], Qp + (size_t)qc * DH64 + c * 32 + g * 8);
     }
 
     float m[QF], l[QF];
@@ -759,7 +773,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
         if (qi < p.nq) {
 #pragma unroll
             for (int df = 0; df < 4; ++df) {
-                const size_t off = ((size_t)s * p.nq + qi) * p.ldo + hh * DH + df * 16 + g * 4;
+                const size_t off = ((size_t)s * p.nq + qi) * p.ldo + hh * DH64 + df * 16 + g * 4;
                 const f32x4 v = o[qf][df] * inv;
                 if (p.out_f32) store4(Of + off, v); else store4(Ot + off, v);
             }
@@ -807,10 +821,10 @@ __global__ __launch_bounds__(64) void attn_small_kernel(const SmallAttnArgs p) {
         f32x4 kx = f32x4{0, 0, 0, 0}, vx = kx;
         if (r < rows) {
             const float* row = p.kv + ((size_t)s0 * p.n + r) * p.ldkv;
-            kx = *reinterpret_cast<const f32x4*>(row + hh * DH + l16 * 4);
-            vx = *reinterpret_cast<const f32x4*>(row + p.h * DH + hh * DH + l16 * 4);
+            kx = *reinterpret_cast<const f32x4*>(row + hh * DH64 + l16 * 4);
+            vx = *reinterpret_cast<const f32x4*>(row + p.h * DH64 + hh * DH64 + l16 * 4);
         }
-        const float ss = group16_sum((kx[0] * kx[0] + kx[1] * kx[1]) + (kx[2] * kx[2] + kx[3] * kx[3]));
+        const float ss = group_sum<16>((kx[0] * kx[0] + kx[1] * kx[1]) + (kx[2] * kx[2] + kx[3] * kx[3]));
         const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
         if (r < rows) {
             f32x4 kn;
@@ -827,7 +841,7 @@ __global__ __launch_bounds__(64) void attn_small_kernel(const SmallAttnArgs p) {
     // q^ = l2norm(q) * q_scale * scale, kept in registers
     f32x4 qv[16];
     {
-        const float* qrow = p.q + ((size_t)s * p.n + i) * p.ldq + hh * DH;
+        const float* qrow = p.q + ((size_t)s * p.n + i) * p.ldq + hh * DH64;
         float ss = 0.f;
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
@@ -878,7 +892,7 @@ __global__ __launch_bounds__(64) void attn_small_kernel(const SmallAttnArgs p) {
         }
     }
     const float inv = 1.0f / l;
-    TO* orow = reinterpret_cast<TO*>(p.O) + ((size_t)s * p.n + i) * p.ldo + hh * DH;
+    TO* orow = reinterpret_cast<TO*>(p.O) + ((size_t)s * p.n + i) * p.ldo + hh * DH64;
 #pragma unroll
     for (int c = 0; c < 16; ++c) store4(orow + c * 4, o[c] * inv);
 }
@@ -888,7 +902,9 @@ using namespace pk;
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-// sizes (in elements of T) the caller must allocate: Qp = S*h*nq_pad*64, Kp = S*h*nk_pad*64, Vt = same as Kp
+static inline bool dim_head_ok(int dh) { return dh == 32 || dh == 64 || dh == 128; }
+
+// sizes (in elements of T) the caller must allocate: Qp = S*h*nq_pad*dim_head, Kp = S*h*nk_pad*dim_head, Vt = same as Kp
 extern "C" int pk_attn_pads(int nq, int n_kv, int nnull, int* nq_pad, int* nk_pad) {
     if (nq <= 0 || n_kv <= 0 || nnull < 0 || !nq_pad || !nk_pad) return PK_EINVAL;
     *nq_pad = round_up(nq, nq >= 256 ? 64 : (nq >= 128 ? 32 : 16));
@@ -896,9 +912,17 @@ extern "C" int pk_attn_pads(int nq, int n_kv, int nnull, int* nq_pad, int* nk_pa
     return PK_OK;
 }
 
-extern "C" int pk_attn_prep(int dtype, const float* q, int ldq, const float* kv, int ldkv, const float* null_kv,
-                            const float* q_scale, const float* k_scale, float scale,
-                            void* Qp, void* Kp, void* Vt, int S, int h, int nq, int n_kv, int nnull, void* stream) {
+template <int DH>
+static void prep_launch(int dtype, unsigned blocks, hipStream_t s, const PrepArgs& p, int nqb) {
+    if (dtype == 1) hipLaunchKernelGGL((prep_qkv_kernel<bf16, DH>), dim3(blocks), dim3(256), 0, s, p, nqb);
+    else if (dtype == 0) hipLaunchKernelGGL((prep_qkv_kernel<float, DH>), dim3(blocks), dim3(256), 0, s, p, nqb);
+    else hipLaunchKernelGGL((prep_qkv_kernel<bf16x3p, DH>), dim3(blocks), dim3(256), 0, s, p, nqb);
+}
+
+extern "C" int pk_attn_prep_dh(int dim_head, int dtype, const float* q, int ldq, const float* kv, int ldkv, const float* null_kv,
+                               const float* q_scale, const float* k_scale, float scale,
+                               void* Qp, void* Kp, void* Vt, int S, int h, int nq, int n_kv, int nnull, void* stream) {
+    if (!dim_head_ok(dim_head) || dtype < 0 || dtype > 2) return PK_EINVAL;
     if (!q || !Qp || S <= 0 || h <= 0) return PK_EINVAL;
     if (kv && (!Kp || !Vt)) return PK_EINVAL;                  // kv == NULL: query side only (cached K/V)
     if (kv && ((q_scale == nullptr) != (k_scale == nullptr))) return PK_EINVAL;      // both NULL: plain dot-product attention (no l2norm)
@@ -911,19 +935,22 @@ extern "C" int pk_attn_prep(int dtype, const float* q, int ldq, const float* kv,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long qrows = (long)S * h * nq_pad;
     const int tiles = (nk_pad + 63) / 64;
-    const unsigned nqb = (unsigned)((qrows + 15) / 16), nkb = kv ? (unsigned)(S * h * tiles) : 0u;
-    if (dtype == 1) {
-        hipLaunchKernelGGL((prep_qkv_kernel<bf16>), dim3(nqb + nkb), dim3(256), 0, s, p, (int)nqb);
-    } else if (dtype == 0) {
-        hipLaunchKernelGGL((prep_qkv_kernel<float>), dim3(nqb + nkb), dim3(256), 0, s, p, (int)nqb);
-    } else if (dtype == 2) {
-        // split-bf16: the images are pre-split (hi | lo) bf16 planes in 128-byte blocks of 32 elements (common.hpp bf16x3p); same sizes
-        // as the f32 images; rows are 64 / nk_pad (% 32 == 0) elements, the bases must sit on a 128-byte boundary
-        if ((reinterpret_cast<uintptr_t>(Qp) & 127) || (kv && ((reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127))) return PK_EALIGN;
-        hipLaunchKernelGGL((prep_qkv_kernel<bf16x3p>), dim3(nqb + nkb), dim3(256), 0, s, p, (int)nqb);
-    } else return PK_EINVAL;
+    const long qrpb = 256 / (dim_head / 4);                    // query rows per block: dim_head / 4 lanes own a row
+    const unsigned nqb = (unsigned)((qrows + qrpb - 1) / qrpb), nkb = kv ? (unsigned)(S * h * tiles) : 0u;
+    // split-bf16: the images are pre-split (hi | lo) bf16 planes in 128-byte blocks of 32 elements (common.hpp bf16x3p); same sizes
+    // as the f32 images; rows are dim_head (one, two or four blocks) / nk_pad (% 32 == 0) elements, the bases must sit on a 128-byte boundary
+    if (dtype == 2 && ((reinterpret_cast<uintptr_t>(Qp) & 127) || (kv && ((reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)))) return PK_EALIGN;
+    if (dim_head == 64) prep_launch<64>(dtype, nqb + nkb, s, p, (int)nqb);
+    else if (dim_head == 32) prep_launch<32>(dtype, nqb + nkb, s, p, (int)nqb);
+    else prep_launch<128>(dtype, nqb + nkb, s, p, (int)nqb);
     PK_CHECK_LAUNCH();
     return PK_OK;
+}
+
+extern "C" int pk_attn_prep(int dtype, const float* q, int ldq, const float* kv, int ldkv, const float* null_kv,
+                            const float* q_scale, const float* k_scale, float scale,
+                            void* Qp, void* Kp, void* Vt, int S, int h, int nq, int n_kv, int nnull, void* stream) {
+    return pk_attn_prep_dh(64, dtype, q, ldq, kv, ldkv, null_kv, q_scale, k_scale, scale, Qp, Kp, Vt, S, h, nq, n_kv, nnull, stream);
 }
 
 #ifdef PK_TIMELINE
@@ -940,30 +967,45 @@ static int n_cu() {
     return n;
 }
 
-// the LDS-free kernel for (dtype, QF query fragments per wave), without (DROP = false) or with attn_dropout
-template <bool DROP>
+// the LDS-free kernel for (dtype, QF query fragments per wave, head width DH), without (DROP = false) or with attn_dropout.
+// attn_qf_max is the largest QF instantiated for (dtype, DH): at DH = 128 the operand fragments and accumulators are twice as many
+// registers, so bf16 stops at 2 and the f32 / split-bf16 operand types (8 registers per fragment) at 1
+static constexpr int attn_qf_max(int dtype, int dh) { return dh == 128 ? (dtype == 1 ? 2 : 1) : (dtype == 1 ? 4 : 2); }
+
+// one (T, QF) instantiation; nothing where attn_qf_max does not build it (attn_fwd_launch refuses those QF before it gets here)
+template <typename T, int QF, bool DROP, int DH>
+static void attn_fwd_one(dim3 grid, dim3 block, hipStream_t s, const AttnArgs& a, const DropParam<DROP>& dr) {
+    if constexpr (QF <= attn_qf_max(sizeof(T) == 2 ? 1 : 0, DH)) hipLaunchKernelGGL((attn_fwd_kernel<T, QF, DROP, DH>), grid, block, 0, s, a, dr);
+}
+
+template <bool DROP, int DH = 64>
 static int attn_fwd_launch(int dtype, int QF, bool images_ok, dim3 grid, dim3 block, hipStream_t s, const AttnArgs& a, const DropParam<DROP>& dr) {
+    if (QF > attn_qf_max(dtype, DH)) return PK_EINVAL;
     if (dtype == 1) {
-        if (QF == 4) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 4, DROP>), grid, block, 0, s, a, dr);
-        else if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16, 2, DROP>), grid, block, 0, s, a, dr);
-        else hipLaunchKernelGGL((attn_fwd_kernel<bf16, 1, DROP>), grid, block, 0, s, a, dr);
+        if (QF == 4) attn_fwd_one<bf16, 4, DROP, DH>(grid, block, s, a, dr);
+        else if (QF == 2) attn_fwd_one<bf16, 2, DROP, DH>(grid, block, s, a, dr);
+        else attn_fwd_one<bf16, 1, DROP, DH>(grid, block, s, a, dr);
     } else if (dtype == 0) {
-        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<float, 2, DROP>), grid, block, 0, s, a, dr);
-        else hipLaunchKernelGGL((attn_fwd_kernel<float, 1, DROP>), grid, block, 0, s, a, dr);
+        if (QF == 2) attn_fwd_one<float, 2, DROP, DH>(grid, block, s, a, dr);
+        else attn_fwd_one<float, 1, DROP, DH>(grid, block, s, a, dr);
     } else if (dtype == 2) {
         if (!images_ok) return PK_EINVAL;
-        if (QF == 2) hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 2, DROP>), grid, block, 0, s, a, dr);
-        else hipLaunchKernelGGL((attn_fwd_kernel<bf16x3p, 1, DROP>), grid, block, 0, s, a, dr);
+        if (QF == 2) attn_fwd_one<bf16x3p, 2, DROP, DH>(grid, block, s, a, dr);
+        else attn_fwd_one<bf16x3p, 1, DROP, DH>(grid, block, s, a, dr);
     } else return PK_EINVAL;
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
 
-static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* Vt,
+static int attn_fwd_impl(int dh, int dtype, const void* Qp, const void* Kp, const void* Vt,
                          const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                          const float* slopes, int causal, void* O, int ldo, int out_is_f32,
                          int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len, const int* pos_code,
                          int code_off, int tab_run4, float score_bound, float* lse, const pk_dropout* drop, void* stream) {
+    if (!dim_head_ok(dh)) return PK_EINVAL;
+    // a width other than 64 runs on the LDS-free kernel only: no bias table, no fixed-offset softmax, no dropout site (the backward kernels are 64-wide)
+    const bool w64 = dh == 64;
+    if (!w64 && (bias_tab || (score_bound == score_bound && fabsf(score_bound) < INFINITY) || drop)) return PK_EINVAL;
     if (!Qp || !Kp || !Vt || !O || S <= 0 || h <= 0) return PK_EINVAL;
     if (drop && (!lse || bias_tab || drop_site_bad(drop) || (unsigned long long)S * h * nq > 0xFFFFFFFFull)) return PK_EINVAL;
     if (bias_tab && (bias || !pos_code || tab_len <= 0 || nnull != 0 || nq != n_kv || causal || kmask)) return PK_EINVAL;
@@ -980,11 +1022,12 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
     static const int qf_cap = [] { const char* e = getenv("PK_ATTN_MAX_QF"); return e ? atoi(e) : 2; }();   // tuning knob (4 measured slower: 146 vs 104 us)
     int QF = (nq >= 256 && dtype == 1) ? 4 : (nq >= 128 ? 2 : 1);
     if (QF > qf_cap && qf_cap >= 1) QF = qf_cap >= 2 ? 2 : 1;
+    if (QF > attn_qf_max(dtype, dh)) QF = attn_qf_max(dtype, dh);
     const long waves = (long)S * h * (nq_pad / (16 * QF));
     dim3 grid((unsigned)((waves + 3) / 4)), block(256);
     static const int use_lds = [] { const char* e = getenv("PK_ATTN_LDS"); return e ? atoi(e) : 1; }();   // tuning knob
     // drop (attn_dropout > 0): every shape goes to the LDS-free kernel below, the LDS-staged forms stay p = 0 only
-    if (!drop && dtype == 1 && use_lds && (!lse || (!bias_tab && !(score_bound == score_bound))) && nnull + n_kv >= 64 && nq >= 64 &&
+    if (w64 && !drop && dtype == 1 && use_lds && (!lse || (!bias_tab && !(score_bound == score_bound))) && nnull + n_kv >= 64 && nq >= 64 &&
         (size_t)S * h * nk_pad * 128 < 0xFFFFFFF0ull) {
         // measured on maskgit self-attention (S*h = 128, n = 576, bias): 16 query rows per wave + bias prefetch 41.2 us,
         // 32 rows per wave 44.5 us (its prefetch spills: 77 us); with a single key tile (n = 64) there is nothing to
@@ -1030,7 +1073,7 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         PK_CHECK_LAUNCH();
         return PK_OK;
     }
-    if (!drop && dtype == 2 && use_lds && !lse && nnull + n_kv >= 64 && nq >= 128 && score_bound == score_bound && fabsf(score_bound) < 1e4f && !kmask && !causal && !bias &&
+    if (w64 && !drop && dtype == 2 && use_lds && !lse && nnull + n_kv >= 64 && nq >= 128 && score_bound == score_bound && fabsf(score_bound) < 1e4f && !kmask && !causal && !bias &&
         out_is_f32 && (size_t)S * h * nk_pad * 256 < 0xFFFFFFF0ull &&
         !((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) {
         // split-bf16 images, fixed-offset softmax (round 3): the same LDS-staged kernel on tiles twice as large (64 KB ring + the bias table:
@@ -1058,7 +1101,7 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
         PK_CHECK_LAUNCH();
         return PK_OK;
     }
-    if (!drop && dtype == 2 && lse && use_lds && nnull == 0 && nq == n_kv && nq >= 128 && !kmask && !causal && out_is_f32 && !bias_tab &&
+    if (w64 && !drop && dtype == 2 && lse && use_lds && nnull == 0 && nq == n_kv && nq >= 128 && !kmask && !causal && out_is_f32 && !bias_tab &&
         (!bias || a.bias_vec) && (size_t)S * h * nk_pad * 256 < 0xFFFFFFF0ull &&
         !((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127)) {
         // training forward, split-bf16 (round 6): the LDS-staged kernel in its RUNNING-MAX form (the fixed-offset form needs a score bound on the
@@ -1087,16 +1130,28 @@ static int attn_fwd_impl(int dtype, const void* Qp, const void* Kp, const void* 
     }
     if (bias_tab) return PK_EINVAL;                       // the table form exists in the LDS-staged kernel only
     const bool images_ok = out_is_f32 && !((reinterpret_cast<uintptr_t>(Qp) | reinterpret_cast<uintptr_t>(Kp) | reinterpret_cast<uintptr_t>(Vt)) & 127);   // what dtype 2 needs
+    if (dh == 32) return attn_fwd_launch<false, 32>(dtype, QF, images_ok, grid, block, s, a, DropParam<false>{});
+    if (dh == 128) return attn_fwd_launch<false, 128>(dtype, QF, images_ok, grid, block, s, a, DropParam<false>{});
     return drop ? attn_fwd_launch<true>(dtype, QF, images_ok, grid, block, s, a, DropParam<true>(drop_keys(*drop)))
                 : attn_fwd_launch<false>(dtype, QF, images_ok, grid, block, s, a, DropParam<false>{});
 }
 
+// dim_head 32 | 64 | 128 (else PK_EINVAL).  64: every kernel below, as pk_attn_fwd.  32 / 128: the LDS-free kernel whatever the shape; a bias
+// table or a finite score_bound is PK_EINVAL there.
+extern "C" int pk_attn_fwd_dh(int dim_head, int dtype, const void* Qp, const void* Kp, const void* Vt,
+                              const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
+                              const float* slopes, int causal, void* O, int ldo, int out_is_f32,
+                              int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len, const int* pos_code,
+                              int code_off, int tab_run4, float score_bound, void* stream) {
+    return attn_fwd_impl(dim_head, dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, bias_tab, tab_len,
+                         pos_code, code_off, tab_run4, score_bound, nullptr, nullptr, stream);
+}
 extern "C" int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void* Vt,
                            const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                            const float* slopes, int causal, void* O, int ldo, int out_is_f32,
                            int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len, const int* pos_code,
                            int code_off, int tab_run4, float score_bound, void* stream) {
-    return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, bias_tab, tab_len,
+    return attn_fwd_impl(64, dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, bias_tab, tab_len,
                          pos_code, code_off, tab_run4, score_bound, nullptr, nullptr, stream);
 }
 // the training forward: the same product, which also writes lse (S h, nq) = the log-sum-exp of every score row -- pk_attn_bwd_ws (flags bit 1) then
@@ -1107,12 +1162,21 @@ extern "C" int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void
 // scores; element (row (s h + hh) nq + i, column j over the nnull + n_kv keys) of the probabilities is kept iff the keep function of stream
 // (seed, offset) says so (keep_thr in [1, 256]: dropped iff its 8-bit draw < keep_thr) and O is scaled by `scale` = 1 / (1 - keep_thr / 256).
 // With a site every shape runs on the LDS-free kernel.
+// dim_head 32 | 64 | 128; a dropout site exists at 64 only (its backward, pk_attn_bwd_ws, is 64-wide): PK_EINVAL with another width.
+extern "C" int pk_attn_fwd_lse_dh(int dim_head, int dtype, const void* Qp, const void* Kp, const void* Vt,
+                                  const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
+                                  const float* slopes, int causal, void* O, int ldo, int out_is_f32,
+                                  int S, int h, int nq, int n_kv, int nnull, float* lse, const pk_dropout* drop, void* stream) {
+    if (!lse) return PK_EINVAL;
+    return attn_fwd_impl(dim_head, dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
+                         nullptr, 0, 0, __builtin_nanf(""), lse, drop, stream);
+}
 extern "C" int pk_attn_fwd_lse(int dtype, const void* Qp, const void* Kp, const void* Vt,
                                const float* bias, long bias_hstride, int bias_ld, const unsigned char* kmask,
                                const float* slopes, int causal, void* O, int ldo, int out_is_f32,
                                int S, int h, int nq, int n_kv, int nnull, float* lse, const pk_dropout* drop, void* stream) {
     if (!lse) return PK_EINVAL;
-    return attn_fwd_impl(dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
+    return attn_fwd_impl(64, dtype, Qp, Kp, Vt, bias, bias_hstride, bias_ld, kmask, slopes, causal, O, ldo, out_is_f32, S, h, nq, n_kv, nnull, nullptr, 0,
                          nullptr, 0, 0, __builtin_nanf(""), lse, drop, stream);
 }
 

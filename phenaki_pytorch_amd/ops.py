@@ -54,11 +54,11 @@ def _peg(x, taps, bias, out, shape, causal):
 
 def _attn_prep(q, kv, null_kv, q_scale, k_scale, scale, qp, kp, vt, dtype, S, heads, n, n_kv):
     nnull = null_kv.shape[1] // 2 if null_kv is not None else 0
-    L.attn_prep(dtype, q, kv, null_kv, q_scale, k_scale, scale, qp, kp, vt, S, heads, n, n_kv, nnull)
+    L.attn_prep(dtype, q, kv, null_kv, q_scale, k_scale, scale, qp, kp, vt, S, heads, n, n_kv, nnull, dim_head=q.shape[-1] // heads)   # 32 | 64 | 128
 
 
 def _attn_fwd(qp, kp, vt, bias, kmask, out, dtype, S, heads, n, n_kv, nnull):
-    L.attn_fwd(dtype, qp, kp, vt, out, S, heads, n, n_kv, nnull, bias=bias, kmask=kmask)
+    L.attn_fwd(dtype, qp, kp, vt, out, S, heads, n, n_kv, nnull, bias=bias, kmask=kmask, dim_head=out.shape[-1] // heads)
     return out
 
 

@@ -37,7 +37,8 @@ import weakref
 import torch
 
 from . import _lib as L
-from .attention import (Attention, FeedForwardSeq, LayerNorm, PEG, compute_dtype_of, exists, pack_linear_weight, resolve_dtype, round_up)
+from .attention import (Attention, FeedForwardSeq, LayerNorm, PEG, compute_dtype_of, exists, pack_linear_weight, require_train_dim_head, resolve_dtype,
+                        round_up)
 
 
 # vocabulary columns per step of the cross-entropy backward (a multiple of 64; tuning knob PK_CE_SLAB)
@@ -821,6 +822,7 @@ def peg_train(peg: PEG, x2d, shape):
 
 
 def attention_train(attn: Attention, x2d, S, n, dtype, *, context2d=None, n_ctx=None, attn_bias=None, kmask=None, img=None):
+    require_train_dim_head(attn)
     drop = L.DropSite.of(attn.attn_dropout, x2d.device)                 # attn_dropout: active iff the module is in training mode and p > 0
     assert not (attn.causal and context2d is not None), 'causal attention is self-attention (attention.py:166-172)'
     cn = attn.context_norm if isinstance(attn.context_norm, LayerNorm) else None
@@ -846,6 +848,7 @@ def position_bias_train(cpb, dims, device):
 def transformer_train(tr, x2d, S, n, dtype, *, video_shape=None, attn_bias=None, context2d=None, n_ctx=None, self_attn_mask=None,
                       cross_attn_context_mask=None):
     """attention.py:315-332 on (S n, D) f32 rows, every block an autograd Function"""
+    require_train_dim_head(tr)
     x = x2d
     wi = transformer_images(tr, dtype)
     wi.refresh()                                                         # ONE launch: every projection weight of the stack, W and W^T images
@@ -865,6 +868,7 @@ def _u8(mask):
 
 def trunk_train(model, ids2d, video_patch_shape, *, context=None, text_mask=None, video_mask=None, use_bias=False, use_cross=True, alpha=1.0):
     """MaskGit.forward(return_embeds=True) / the TokenCritic trunk with gradients: (b n, D) f32 rows of norm_out"""
+    require_train_dim_head(model)
     b, n = ids2d.shape
     dt = compute_dtype_of(model)
     x = _Embed.apply(model.token_emb.weight, model.pos_emb.weight, ids2d.long().contiguous(), float(alpha))
@@ -929,6 +933,7 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
     `cond_drop_prob` is accepted for signature compatibility and HAS NO EFFECT: the reference overwrites it with 0 before use
     (phenaki_pytorch.py:594 shadows the argument), so classifier-free-guidance dropout never fires in its training step either."""
     from .phenaki import SelfCritic, TokenCritic
+    require_train_dim_head(ph.maskgit, ph.critic)                       # before the tokenizer or anything else launches
     assert not (only_train_generator and only_train_critic)
     assert not (only_train_critic and not exists(ph.critic)), 'only_train_critic needs a critic (Phenaki(critic=...) or self_token_critic=True)'
     assert exists(videos) ^ exists(video_codebook_ids), 'either raw video or video codebook ids must be given'

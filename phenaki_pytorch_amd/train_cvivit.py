@@ -35,7 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .attention import compute_dtype_of
+from .attention import compute_dtype_of, require_train_dim_head
 from .discriminator import PickFrame, bce_discr_loss, bce_gen_loss, gradient_penalty, hinge_discr_loss, hinge_gen_loss
 from .train import _Linear, _f32, linear_bwd, linear_fwd, position_bias_train, transformer_train
 
@@ -317,6 +317,7 @@ def _patch_embed_train(seq, video, geom, dtype):
 
 def cvivit_loss_train(cv, video, *, mask=None, return_recons=False):
     """CViViT.forward (cvivit.py:518-627, use_vgg_and_gan = False) with an autograd graph over the C-ViViT parameters"""
+    require_train_dim_head(cv)
     if cv.use_vgg_and_gan:
         assert torch.is_grad_enabled(), 'the GAN objective differentiates its terms for the adaptive weight (cvivit.py:657-662): call it with grad mode on'
         assert cv.vgg is not None, ('the perceptual loss needs a feature network: pass CViViT(vgg=<nn.Module>) -- the reference default, '
