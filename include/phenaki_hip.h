@@ -179,6 +179,31 @@ int pk_lfq_aux_grad(const float* proj, const float* GA, const float* GB, int M, 
 int pk_lfq_aux_finish(const float* ent, const float* commit, int M, const float* hc_part, int cd, float w_e, float gamma, float w_c, float* out,
                       void* stream);
 
+/* Training step of the cosine-sim VectorQuantize (constructed at cvivit.py:321, called at cvivit.py:568-570; the un-vendored vector-quantize-pytorch
+ * module in training mode, semantics restated in DESIGN.md "VectorQuantize training"): straight-through output q = E[ids], commitment loss
+ * w mean_kept (q - x)^2, EMA update of cluster_size / embed_avg / embed from the kept rows.  x, xn = l2norm(x), y, dy, dx are contiguous (M, D) f32,
+ * E / embed_avg / embed contiguous (V, D) f32, D % 4 == 0 and D <= 1024, 16-byte aligned bases; ids (M,) int64; keep (M,) bytes, NULL = every row kept.
+ * Every kernel tests 0 <= id < V on the device and treats a row with another id as dropped (it is never used as an index).
+ *   pk_vq_hist:            counts[c] (V int32, ZEROED by the caller) += #{kept r : ids[r] = c} (integer atomics: order-independent).  check_ids != 0:
+ *                          the ids are first copied to the host (synchronises the stream) and an id outside [0, V) is PK_EINVAL with nothing launched.
+ *   pk_vq_scan:            offsets = cursor = exclusive scan of counts; cluster_size = decay cluster_size + (1 - decay) counts in place;
+ *                          S[0] = sum_c cluster_size[c] in a fixed order (one workgroup, no host read).
+ *   pk_vq_fill:            rows[atomicAdd(cursor[id], 1)] = r for every kept row: code c's rows are rows[offsets[c] .. + counts[c]), in any order.
+ *   pk_vq_codebook_update: per code c, sum[c] = sum of xn[r] over its rows in ASCENDING r (bit-reproducible), embed_avg[c] = decay embed_avg[c] +
+ *                          (1 - decay) sum[c], embed[c] = l2norm(embed_avg[c] / ((cluster_size[c] + eps) / (S + V eps) S)) (l2norm eps 1e-12); in place.
+ *   pk_vq_gather_commit:   y[r] = E[ids[r]]; rowsq[r] = sum_d (y - x)^2 for kept rows, 0 for dropped ones (summed by pk_colsum).
+ *   pk_vq_commit_bwd:      dx = dy + coef * coef_dev[0] (coef_dev NULL: 1) * keep[r] * (x[r] - q[r]), q = the y of pk_vq_gather_commit (the codebook
+ *                          itself has been updated in place by the time the backward pass runs, so the gather is not repeated from it). */
+int pk_vq_hist(const long long* ids, const unsigned char* keep, int M, int V, int* counts, int check_ids, void* stream);
+int pk_vq_scan(const int* counts, int V, float decay, float* cluster_size, int* offsets, int* cursor, float* S, void* stream);
+int pk_vq_fill(const long long* ids, const unsigned char* keep, int M, int V, int* cursor, int* rows, void* stream);
+int pk_vq_codebook_update(const float* xn, const int* counts, const int* offsets, const int* rows, const float* cluster_size, const float* S,
+                          int M, int V, int D, float decay, float eps, float* embed_avg, float* embed, void* stream);
+int pk_vq_gather_commit(const float* x, const float* E, const long long* ids, const unsigned char* keep, int M, int V, int D, float* y,
+                        float* rowsq, void* stream);
+int pk_vq_commit_bwd(const float* dy, const float* x, const float* q, const unsigned char* keep, int M, int D, float coef, const float* coef_dev,
+                     float* dx, void* stream);
+
 /* Text-encoder support (reference t5.py:64-103 calls HuggingFace T5EncoderModel; the T5 v1.1 encoder layers are built
  * from pk_gemm, pk_attn_prep with q_scale = k_scale = NULL (plain dot-product attention: no l2norm, q * scale), pk_attn_fwd and these two):
  * pk_rmsnorm: T5LayerNorm, y = x * rsqrt(mean(x^2) + eps) * w (f32 statistics, no mean subtraction, no bias); rows with rowmask[row] == 0

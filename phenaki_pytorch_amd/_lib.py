@@ -50,6 +50,12 @@ SIGNATURES = {
     'pk_lfq_aux_codebook': [_P, _I, _F, _F, _P, _P, _P],
     'pk_lfq_aux_grad': [_P, _P, _P, _I, _I, _F, _F, _F, _F, _P, _P],
     'pk_lfq_aux_finish': [_P, _P, _I, _P, _I, _F, _F, _F, _P, _P],
+    'pk_vq_hist': [_P, _P, _I, _I, _P, _I, _P],
+    'pk_vq_scan': [_P, _I, _F, _P, _P, _P, _P, _P],
+    'pk_vq_fill': [_P, _P, _I, _I, _P, _P, _P],
+    'pk_vq_codebook_update': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
+    'pk_vq_gather_commit': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    'pk_vq_commit_bwd': [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P],
     'pk_layernorm_lfq': [_P, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'pk_embed': [_P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P],
     'pk_cpb_input': [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -378,6 +384,43 @@ def lfq_aux(proj, *, inv_temperature=100., codebook_scale=1., entropy_loss_weigh
     _check(lib.pk_lfq_aux_grad(ptr(proj), ptr(GA), ptr(GB), M, cd, alpha, float(codebook_scale), w_e / M, 2. * w_c / (M * cd), ptr(dproj), st), 'pk_lfq_aux_grad')
     _check(lib.pk_lfq_aux_finish(ptr(ent), ptr(commit), M, ptr(hc), cd, w_e, gamma, w_c, ptr(out), st), 'pk_lfq_aux_finish')
     return out, dproj
+
+
+def vq_gather_commit(x, E, ids, keep, y, rowsq):
+    """y[r] = E[ids[r]]; rowsq[r] = sum_d (y[r] - x[r])^2 for the rows `keep` (M,) uint8 keeps (None: all), 0 for the others"""
+    M, D = x.shape
+    rc = load().pk_vq_gather_commit(f32p(x, 'x'), f32p(E, 'codebook'), ptr(ids), ptr(keep), M, E.shape[0], D, ptr(y), ptr(rowsq), stream(x))
+    _check(rc, 'pk_vq_gather_commit')
+
+
+def vq_commit_bwd(dy, x, q, keep, coef, coef_dev, dx):
+    """dx = dy + coef * coef_dev[0] * keep[r] * (x - q), q = the rows vq_gather_commit wrote"""
+    M, D = x.shape
+    rc = load().pk_vq_commit_bwd(f32p(dy, 'dy'), f32p(x, 'x'), f32p(q, 'q'), ptr(keep), M, D, float(coef), f32p(coef_dev, 'd commit'), ptr(dx), stream(x))
+    _check(rc, 'pk_vq_commit_bwd')
+    return dx
+
+
+def vq_ema_update(xn, ids, keep, cluster_size, embed_avg, embed, decay, eps, check_ids=False):
+    """EMA codebook update of the cosine-sim VectorQuantize, in place on cluster_size (V,), embed_avg (V, D), embed (V, D), from the kept rows of
+    xn (M, D) = l2norm(x) and their ids: counting sort by id (pk_vq_hist / scan / fill), then one wave per code (pk_vq_codebook_update).
+    Returns counts (V,) int32 = the bins of this step."""
+    lib = load()
+    M, D = xn.shape
+    V = embed.shape[0]
+    dev = xn.device
+    st = stream(xn)
+    counts = torch.zeros((V,), device=dev, dtype=torch.int32)
+    offsets, cursor = torch.empty_like(counts), torch.empty_like(counts)
+    rows = torch.empty((M,), device=dev, dtype=torch.int32)
+    S = torch.empty((1,), device=dev, dtype=torch.float32)
+    cs, ea, em = f32p(cluster_size, 'cluster_size'), f32p(embed_avg, 'embed_avg'), f32p(embed, 'embed')
+    _check(lib.pk_vq_hist(ptr(ids), ptr(keep), M, V, ptr(counts), 1 if check_ids else 0, st), 'pk_vq_hist')
+    _check(lib.pk_vq_scan(ptr(counts), V, float(decay), cs, ptr(offsets), ptr(cursor), ptr(S), st), 'pk_vq_scan')
+    _check(lib.pk_vq_fill(ptr(ids), ptr(keep), M, V, ptr(cursor), ptr(rows), st), 'pk_vq_fill')
+    _check(lib.pk_vq_codebook_update(f32p(xn, 'xn'), ptr(counts), ptr(offsets), ptr(rows), cs, ptr(S), M, V, D, float(decay), float(eps), ea, em, st),
+           'pk_vq_codebook_update')
+    return counts
 
 
 def embed(ids, tok, pos, out, S, n, D, *, nb=None, ids_prime=None, out_t=None):

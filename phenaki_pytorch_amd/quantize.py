@@ -113,38 +113,54 @@ class _CosineSimCodebook(nn.Module):
 
 
 class VectorQuantize(nn.Module):
-    """`vector_quantize_pytorch.VectorQuantize(dim, codebook_size, use_cosine_sim=True)` at inference
+    """`vector_quantize_pytorch.VectorQuantize(dim, codebook_size, use_cosine_sim=True)`
     (reference call sites cvivit.py:321 construct, :568-570 forward with `mask=`, :441 `.codebook[indices]`; the
-    package is not vendored -- published eval behaviour: l2-normalise the input, argmax of its dot product with the
-    unit-norm codebook, gather; restated in oracle/lfq.py).  The lookup is the vocab-head kernel in its no-noise mode
+    package is not vendored -- published behaviour: l2-normalise the input, argmax of its dot product with the
+    unit-norm codebook, gather; the eval half restated in oracle/lfq.py, the training half in DESIGN.md
+    "VectorQuantize training").  The lookup is the vocab-head kernel in its no-noise mode
     (one fused GEMM + argmax, the (M, 65536) similarity matrix is never written) and always runs in exact f32: ids are
-    an argmax over 65 536 cosine similarities."""
+    an argmax over 65 536 cosine similarities.
 
-    def __init__(self, *, dim, codebook_size, use_cosine_sim=True, **_unused):
+    Training mode (`self.training`, the predicate of LFQ.forward): the straight-through output, the commitment loss
+    commitment_weight * mean (q - x)^2 and the EMA update (decay, eps) of the `_codebook` buffers cluster_size /
+    embed_avg / embed from the rows `mask` keeps -- train_cvivit._VQFn on the pk_vq_* kernels.  One head, no
+    projections, no k-means initialisation, no dead-code expiry, statistics per rank."""
+
+    def __init__(self, *, dim, codebook_size, use_cosine_sim=True, decay=0.8, eps=1e-5, commitment_weight=1.0, **_unused):
         super().__init__()
         assert use_cosine_sim, 'only the cosine-sim codebook (the reference construction, cvivit.py:321) is built'
         assert dim % 32 == 0 and codebook_size % 4 == 0
+        assert 0. <= decay <= 1. and eps > 0.
         self.dim, self.codebook_size = dim, codebook_size
+        self.decay, self.eps, self.commitment_weight = float(decay), float(eps), float(commitment_weight)
         self._codebook = _CosineSimCodebook(dim, codebook_size)
 
     @property
     def codebook(self):
         return self._codebook.embed[0]
 
-    def encode_ids(self, x2d, return_proj=False):
-        assert not return_proj, 'the margin audit projection exists for LFQ only'
+    def normalised(self, x2d):
+        """x2d (M, dim) f32 -> its rows at unit l2 norm (the query side of the lookup, and what the EMA update averages)"""
         L.require_device(x2d, 'tokens')
         M, D = x2d.shape
-        V = self.codebook_size
         xn = torch.empty_like(x2d)
         L.l2norm_rows(x2d, xn, M, D)
+        return xn
+
+    def ids_of_normalised(self, xn):
+        M, D = xn.shape
+        V = self.codebook_size
         cb = self.codebook.contiguous()
-        zero_bias = torch.zeros((V,), device=x2d.device, dtype=torch.float32)
-        partials = torch.empty((5 * L.vocab_ntiles(V) * M,), device=x2d.device, dtype=torch.float32)
+        zero_bias = torch.zeros((V,), device=xn.device, dtype=torch.float32)
+        partials = torch.empty((5 * L.vocab_ntiles(V) * M,), device=xn.device, dtype=torch.float32)
         L.vocab_sample(L.F32, xn, cb, zero_bias, M, V, D, 1.0, None, None, 0, False, partials, no_noise=True)
-        ids = torch.empty((M,), device=x2d.device, dtype=torch.int64)
+        ids = torch.empty((M,), device=xn.device, dtype=torch.int64)
         L.vocab_reduce(partials, M, V, None, None, None, ids, None, False)
         return ids
+
+    def encode_ids(self, x2d, return_proj=False):
+        assert not return_proj, 'the margin audit projection exists for LFQ only'
+        return self.ids_of_normalised(self.normalised(x2d))
 
     def codes_2d(self, ids_flat, *, ids_prime=None, perm=(0, 0)):
         if ids_prime is not None:
@@ -156,8 +172,16 @@ class VectorQuantize(nn.Module):
         return codes
 
     def forward(self, x, mask=None, **_unused):
+        """(b, n, dim) -> (quantized (b, n, dim), indices (b, n) int64, commitment loss).  mask (b, n) bool: the rows that enter the commitment
+        loss and the codebook statistics (every row gets an id and a code).  eval mode: the hard codes, no gradient, no update, loss 0; training
+        mode: straight-through gradient, the commitment loss and the in-place EMA update -- under no_grad the same values and the same update
+        without a graph."""
         b, n, d = x.shape
         x2 = x.reshape(b * n, d).float().contiguous()
+        if self.training:
+            from .train_cvivit import _VQFn
+            q, commit, ids = _VQFn.apply(x2, self, None if mask is None else mask.reshape(b * n), True)
+            return q.reshape(b, n, d), ids.reshape(b, n), commit
         ids = self.encode_ids(x2)
         q = self.codes_2d(ids)
         return q.reshape(b, n, d), ids.reshape(b, n), torch.zeros((), device=x.device)

@@ -15,6 +15,9 @@ forward and backward kernels, the PEG with causal frame padding); this file adds
     _GatherRows     '(b t) (h w)' <-> '(b h w) t' token order                           pk_pack (row gather) both ways
     _MergeFrames / _SplitFrames   first-frame rows | remaining rows <-> (b, t, h w)     pk_scatter_rows / pk_pack
     _LFQFn          project_in -> sign -> project_out, gradient straight through        pk_lfq_encode, pk_sign, pk_lfq_decode / pk_pack + pk_gemm
+    _VQFn           lookup_free_quantization=False: l2norm -> cosine argmax -> codebook    pk_l2norm_rows, pk_vocab_sample / pk_vocab_reduce,
+                    row straight through, commitment loss, EMA codebook update           pk_vq_gather_commit / pk_vq_commit_bwd, pk_vq_hist / scan / fill /
+                                                                                         codebook_update
     _PatchMSE       mean (to_pixels(tokens) - patches(video))^2 -- un-patchify is a     pk_patchify_ln (raw rows), pk_sqdiff_partials
                     bijection of the pixels, so the loss is taken in patch layout        / pk_scaled_diff
 
@@ -206,6 +209,72 @@ class _LFQFn(torch.autograd.Function):
         return dx, dWp, dbp, dWo, dbo, None, None
 
 
+_WARNED_VQ_PER_RANK = False
+
+
+def _warn_vq_statistics_per_rank():
+    global _WARNED_VQ_PER_RANK
+    import torch.distributed as dist
+    if not _WARNED_VQ_PER_RANK and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        import warnings
+        warnings.warn('VectorQuantize training: the EMA codebook statistics (bins, sums) are NOT all-reduced across ranks -- every rank updates its '
+                      'codebook from its own rows (INTEGRATION.md)', RuntimeWarning, stacklevel=3)
+        _WARNED_VQ_PER_RANK = True
+
+
+class _VQFn(torch.autograd.Function):
+    """The cosine-sim `VectorQuantize` (quantize.py) in training mode -- the published module's semantics as restated in DESIGN.md "VectorQuantize
+    training" (call site cvivit.py:568-570; parity with the un-vendored package unpinned).  x (M, D) f32 rows, keep (M,) bool or None:
+        ids = argmax_c l2norm(x) . E[c] by the exact-f32 lookup of the inference path (the ids the tokenizer emits); every row gets one;
+        y = E[ids], gathered BEFORE the update; backward dx = dy (straight through);
+        commit = commitment_weight * mean over the kept rows of (y - x)^2, y detached: kept rows get d commit * w * 2 (x - y) / (n_keep D);
+        the EMA update of cluster_size / embed_avg / embed from the kept rows, in place, in every call (grad mode or not), never differentiated.
+    Returns (y, ids), or (y, commit, ids) with want_commit; ids is not differentiable.  The backward pass reads the code rows back from y itself:
+    the codebook has moved on by then."""
+
+    @staticmethod
+    def forward(ctx, x, vq, keep=None, want_commit=False):
+        M, D = x.shape
+        dev = x.device
+        cb = vq._codebook
+        n_keep = M
+        if keep is not None:
+            L.require_device(keep, 'mask')
+            keep = keep.reshape(-1).to(torch.uint8).contiguous()
+            assert keep.numel() == M, f'the row mask has {keep.numel()} entries for {M} rows'
+            n_keep = int(keep.sum().item())                          # (one host read per masked step: the divisor of the mean)
+            if n_keep == 0:
+                raise ValueError('VectorQuantize training step: the mask keeps no row')
+        _warn_vq_statistics_per_rank()
+        x = x.detach()
+        xn = vq.normalised(x)
+        ids = vq.ids_of_normalised(xn)
+        E = cb.embed[0]
+        y, rowsq = _f32((M, D), dev), _f32((M,), dev)
+        L.vq_gather_commit(x, E, ids, keep, y, rowsq)
+        L.vq_ema_update(xn, ids, keep, cb.cluster_size[0], cb.embed_avg[0], E, vq.decay, vq.eps)
+        for buf in (cb.cluster_size, cb.embed_avg, cb.embed):
+            torch.autograd.graph.increment_version(buf)             # the kernels wrote through raw pointers
+        ctx.mark_non_differentiable(ids)
+        ctx.want_commit = bool(want_commit)
+        if not want_commit:
+            return y, ids
+        scale = vq.commitment_weight / (float(n_keep) * D)
+        commit = L.colsum(rowsq.view(M, 1), M, 1, _f32((1,), dev), scale=scale).reshape(())
+        ctx.save_for_backward(x, y, keep)
+        ctx.coef = 2. * scale
+        return y, commit, ids
+
+    @staticmethod
+    def backward(ctx, dy, *rest):
+        dcommit = rest[0] if ctx.want_commit else None
+        if dcommit is None:
+            return dy, None, None, None
+        x, y, keep = ctx.saved_tensors
+        dx = L.vq_commit_bwd(dy.contiguous(), x, y, keep, ctx.coef, dcommit.detach().float().reshape(1).contiguous(), _f32(tuple(x.shape), x.device))
+        return dx, None, None, None
+
+
 class _PatchMSE(torch.autograd.Function):
     """F.mse_loss(video, recon) (cvivit.py:591) with recon = un-patchify(pix): every pixel of the video is exactly one element of one patch row,
     so mean (video - recon)^2 = [sum_g sum (pix_g - patches_g(video))^2] / video.numel() -- the reconstruction is never laid out as a video."""
@@ -284,6 +353,29 @@ def _three_channels(t):
     return t.expand(-1, 3, -1, -1) if t.shape[1] == 1 else t       # grayscale for the VGG (cvivit.py:640-641)
 
 
+def temporal_row_mask(token_mask, T, hw):
+    """token mask (b, T h w) in '(t h w)' order (calculate_video_token_mask, cvivit.py:365-373) -> (b h w T,) in the '(b h w) t' row order the
+    quantizer sees inside the training step"""
+    b = token_mask.shape[0]
+    return token_mask.reshape(b, T, hw).permute(0, 2, 1).reshape(-1)
+
+
+def _vq_train_recon(cv, video, mask):
+    """the reconstruction of cvivit_discr_loss for a training-mode cosine-sim VectorQuantize: the published module updates its codebook in this call
+    too (cvivit.py:570 runs before the branch of :605), and the decoder reads the codes gathered BEFORE that update.  No graph."""
+    is_image = video.ndim == 4
+    video = cv._check_video(video, mask)
+    L.require_device(video, 'video')
+    video = video.float().contiguous()
+    b = video.shape[0]
+    tokens, T = cv._patch_embed(video)
+    tokens = cv._encode2d(tokens, b, T, xt=cv.__dict__.pop('_pk_tokens_t', None))                     # rows '(b t) (h w)'
+    keep = None if mask is None else cv.calculate_video_token_mask(video, mask).reshape(-1)
+    codes, _ = _VQFn.apply(tokens, cv.vq, keep, False)
+    recon = cv._decode2d(codes, b, T)
+    return recon.squeeze(2) if is_image else recon
+
+
 def cvivit_discr_loss(cv, video, *, mask=None, apply_grad_penalty=True, return_recons=False):
     """CViViT.forward(video, return_discr_loss=True) (cvivit.py:604-622): hinge (or BCE) loss of the discriminator on one random frame per sample of
     the video and of its DETACHED reconstruction, plus the gradient penalty on the real frames.  The tokenizer runs without a graph (the
@@ -291,7 +383,10 @@ def cvivit_discr_loss(cv, video, *, mask=None, apply_grad_penalty=True, return_r
     assert cv.discr is not None, 'discriminator must exist to train it'
     is_image = video.ndim == 4
     with torch.no_grad():
-        recon = cv._forward(video, mask, return_recons_only=True)
+        if not cv.lookup_free_quantization and cv.vq.training:
+            recon = _vq_train_recon(cv, video, mask)
+        else:
+            recon = cv._forward(video, mask, return_recons_only=True)
     if is_image:
         video, recon = video.unsqueeze(2), recon.unsqueeze(2)
     video = video.detach().float().contiguous()
@@ -322,7 +417,6 @@ def cvivit_loss_train(cv, video, *, mask=None, return_recons=False):
         assert torch.is_grad_enabled(), 'the GAN objective differentiates its terms for the adaptive weight (cvivit.py:657-662): call it with grad mode on'
         assert cv.vgg is not None, ('the perceptual loss needs a feature network: pass CViViT(vgg=<nn.Module>) -- the reference default, '
                                     "torchvision's pretrained VGG16 (cvivit.py:346-352), is not available offline")
-    assert cv.lookup_free_quantization, 'the training step is built for the LFQ tokenizer (the reference default)'
     is_image = video.ndim == 4
     if is_image:
         video = video.unsqueeze(2)
@@ -351,10 +445,20 @@ def cvivit_loss_train(cv, video, *, mask=None, return_recons=False):
     # quantize (row-wise: the token order does not matter), then decode: temporal, then spatial (cvivit.py:476-516)
     vq = cv.vq
     vq_aux = None
-    # the published LFQ's predicate is its own `training` flag (the same predicate as quantize.LFQ.forward): in eval() it returns the hard
-    # codes with NO straight-through gradient and aux = 0, also inside a grad-mode forward of a GAN-mode tokenizer
+    # the published quantizers' predicate is their own `training` flag (the same predicate as quantize.LFQ.forward): in eval() they return the
+    # hard codes with NO straight-through gradient and aux = 0, also inside a grad-mode forward of a GAN-mode tokenizer
     vq_train = bool(getattr(vq, 'training', True))
-    if cv.use_vgg_and_gan and hasattr(vq, 'aux_config') and vq_train:
+    if not cv.lookup_free_quantization:
+        # the cosine-sim VectorQuantize (cvivit.py:564-570): rows of the kept token frames enter the commitment loss and the codebook statistics
+        if vq_train:
+            keep = None if mask is None else temporal_row_mask(cv.calculate_video_token_mask(video, mask), T, hw)
+            if cv.use_vgg_and_gan:
+                x, vq_aux, _ = _VQFn.apply(x, vq, keep, True)           # the generator objective adds the commitment loss (cvivit.py:666)
+            else:
+                x, _ = _VQFn.apply(x, vq, keep, False)                   # cvivit.py:629-633 never reads it; the codebook is updated all the same
+        else:
+            x = vq.codes_2d(vq.encode_ids(x.detach()))                   # eval(): hard codes, no gradient to the encoder, no update, aux 0
+    elif cv.use_vgg_and_gan and hasattr(vq, 'aux_config') and vq_train:
         # the generator objective adds the quantizer's auxiliary loss (cvivit.py:570, :666); the reconstruction-only objective never reads it
         x, vq_aux, _ = _LFQFn.apply(x, vq.project_in.weight, vq.project_in.bias, vq.project_out.weight, vq.project_out.bias, vq.aux_config())
     else:
@@ -401,7 +505,7 @@ def cvivit_loss_train(cv, video, *, mask=None, return_recons=False):
             # a 4-D image batch never reaches to_pixels (only to_pixels_first_frame): both gradient norms are 0 -> safe_div gives 0
             adaptive = torch.zeros((), device=dev)
         # cvivit.py:666: loss = recon_loss + perceptual_loss + vq_aux_loss + adaptive_weight * gen_loss (vq_aux_loss: the LFQ's entropy +
-        # commitment terms, pk_lfq_aux_*; 0 for the cosine-sim VectorQuantize at inference semantics)
+        # commitment terms, pk_lfq_aux_*, or the cosine-sim VectorQuantize's commitment loss, pk_vq_gather_commit; 0 in eval mode)
         loss = loss + perceptual + adaptive * gen_loss
         if vq_aux is not None:
             loss = loss + vq_aux
