@@ -1082,20 +1082,14 @@ static int attn_fwd_impl(int dh, int dtype, const void* Qp, const void* Kp, cons
         const uint32_t kv_bytes = (uint32_t)((size_t)S * h * nk_pad * 256);
         const size_t lds = (size_t)2 * 32768 + (bias_tab ? (((size_t)tab_len * 4 + 15) & ~(size_t)15) + (((size_t)n_kv * 4 + 15) & ~(size_t)15) : 0);
         if (lds > 160 * 1024) return PK_EINVAL;
-        static bool attr_tab = false, attr_plain = false;
+        static pk::LdsOptIn lds_tab, lds_plain;
         a.off2 = ceilf(score_bound * ATTN_LOG2E);
         dim3 g2((unsigned)(S * h * qblocks));
         if (bias_tab) {
-            if (!attr_tab) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<2, false, true, true, bf16x3p>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PK_ELAUNCH;
-                attr_tab = true;
-            }
+            if (lds_tab.raise(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<2, false, true, true, bf16x3p>), 160 * 1024) != PK_OK) return PK_ELAUNCH;
             hipLaunchKernelGGL((attn_fwd_lds_kernel<2, false, true, true, bf16x3p>), g2, block, lds, s, a, kv_bytes);
         } else {
-            if (!attr_plain) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<2, false, false, true, bf16x3p>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PK_ELAUNCH;
-                attr_plain = true;
-            }
+            if (lds_plain.raise(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<2, false, false, true, bf16x3p>), 160 * 1024) != PK_OK) return PK_ELAUNCH;
             hipLaunchKernelGGL((attn_fwd_lds_kernel<2, false, false, true, bf16x3p>), g2, block, lds, s, a, kv_bytes);
         }
         PK_CHECK_LAUNCH();
@@ -1109,12 +1103,9 @@ static int attn_fwd_impl(int dh, int dtype, const void* Qp, const void* Kp, cons
         // writes lse.  The LDS-free kernel it replaces streams K / V^T through L1 per wave: 104-120 us at S h = 64, n = 576.
         static const bool on = !(getenv("PK_ATTN_TRAIN_LDS") && getenv("PK_ATTN_TRAIN_LDS")[0] == '0');      // A/B switch
         if (on) {
-            static bool attr = false;
-            if (!attr) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<2, false, false, false, bf16x3p>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PK_ELAUNCH;
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<3, false, false, false, bf16x3p>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PK_ELAUNCH;
-                attr = true;
-            }
+            static pk::LdsOptIn lds2, lds3;
+            if (lds2.raise(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<2, false, false, false, bf16x3p>), 160 * 1024) != PK_OK ||
+                lds3.raise(reinterpret_cast<const void*>(&attn_fwd_lds_kernel<3, false, false, false, bf16x3p>), 160 * 1024) != PK_OK) return PK_ELAUNCH;
             // one workgroup per CU (the 64 KB ring, one wave per SIMD): 128-row workgroups are 5 per head at n = 576, i.e. 320 for the 64 (sequence, head)
             // pairs of a B = 8 step = two rounds on 256 CUs; 192-row workgroups (48 rows per wave) are 192 = one round
             static const int qf_env = [] { const char* e = getenv("PK_ATTN_TRAIN_QF"); return e ? atoi(e) : 0; }();

@@ -658,19 +658,17 @@ extern "C" int pk_attn_bwd_work(int S, int heads, int n, int n_kv, int nnull) {
     return G > 1 ? (int)(2L * G * S * heads * (nnull + n_kv) * 64) : 0;          // G > 1 only below 384 key tiles: < 2^24 floats
 }
 // kernel Q then kernel KV in product form X3 (0: f32, 1: split-bf16, 2: single bf16 products), without (DROP = false) or with attn_dropout.
-// The dynamic-LDS limits of a DROP value's six kernels are raised on its first use.
+// The dynamic-LDS limits of a DROP value's six kernels are raised on its first use on each device.
 template <bool DROP>
 static int attn_bwd_launch(int X3, dim3 gq, dim3 gk, hipStream_t s, const AttnBwdArgs& p, const DropParam<DROP>& dr) {
-    static bool attr_done = false;
-    if (!attr_done) {
+    static pk::LdsOptIn lds_q[3], lds_kv[3];
+    {
         const void* const kq[3] = {reinterpret_cast<const void*>(&attn_bwd_q_kernel<0, DROP>), reinterpret_cast<const void*>(&attn_bwd_q_kernel<1, DROP>),
                                    reinterpret_cast<const void*>(&attn_bwd_q_kernel<2, DROP>)};
         const void* const kk[3] = {reinterpret_cast<const void*>(&attn_bwd_kv_kernel<0, DROP>), reinterpret_cast<const void*>(&attn_bwd_kv_kernel<1, DROP>),
                                    reinterpret_cast<const void*>(&attn_bwd_kv_kernel<2, DROP>)};
         for (int i = 0; i < 3; ++i)
-            if (hipFuncSetAttribute(kq[i], hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TSZ * 4) != hipSuccess ||
-                hipFuncSetAttribute(kk[i], hipFuncAttributeMaxDynamicSharedMemorySize, KV_SMEM) != hipSuccess) return PK_ELAUNCH;
-        attr_done = true;
+            if (lds_q[i].raise(kq[i], 4 * TSZ * 4) != PK_OK || lds_kv[i].raise(kk[i], KV_SMEM) != PK_OK) return PK_ELAUNCH;
     }
     if (X3 == 2) {
         hipLaunchKernelGGL((attn_bwd_q_kernel<2, DROP>), gq, dim3(256), 4 * TSZ * 4, s, p, dr);

@@ -324,3 +324,20 @@ constexpr float NEG_MAX = -3.402823466e+38f;   // -finfo(float32).max, the refer
 #define PK_ELAUNCH (-3)      // hipGetLastError() after the launch was not hipSuccess
 
 #define PK_CHECK_LAUNCH() do { if (hipGetLastError() != hipSuccess) return PK_ELAUNCH; } while (0)
+
+// Opt-in of one kernel to `bytes` (> 64 KB) of dynamic LDS.  The limit is raised per kernel AND per device of the process, so every call site keeps
+// one `static pk::LdsOptIn` per kernel and calls raise() ahead of the launch: the attribute is set on the first launch on each device.
+namespace pk {
+struct LdsOptIn {
+    bool done[64] = {};
+    int raise(const void* kernel, int bytes) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
+        if (!done[dev]) {
+            if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return PK_ELAUNCH;
+            done[dev] = true;
+        }
+        return PK_OK;
+    }
+};
+}  // namespace pk

@@ -334,15 +334,9 @@ static int launch_v1(const GemmOperands& p, const GemmEpilogue& e, hipStream_t s
 template <typename T, int TM, int TN, int STAGES, int WM = 2, int WN = 2, int ROWB = 128, int PW = 0, int LNF = 0>
 static int launch_dma(const GemmOperands& p, const GemmEpilogue& e, int a_nrows, hipStream_t s) {
     using Tile = GemmDma<T, TM, TN, WM, WN, STAGES, ROWB, PW>;
-    if (Tile::SMEM > 65536) {                              // opt-in to > 64 KB of LDS: per kernel AND per device of the process
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
-        if (!attr_set[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dma_kernel<T, TM, TN, WM, WN, STAGES, ROWB, PW, LNF>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, Tile::SMEM) != hipSuccess) return PK_ELAUNCH;
-            attr_set[dev] = true;
-        }
+    if (Tile::SMEM > 65536) {
+        static LdsOptIn lds;
+        if (lds.raise(reinterpret_cast<const void*>(&gemm_dma_kernel<T, TM, TN, WM, WN, STAGES, ROWB, PW, LNF>), Tile::SMEM) != PK_OK) return PK_ELAUNCH;
     }
     const int MT = (p.M + Tile::BM - 1) / Tile::BM, NT = (p.N + Tile::BN - 1) / Tile::BN;
     dim3 grid(8 * ((MT + 7) / 8) * NT);                   // see the XCD-aware tile map in the kernel
@@ -354,14 +348,10 @@ static int launch_dma(const GemmOperands& p, const GemmEpilogue& e, int a_nrows,
     return PK_OK;
 }
 
-// 256 x 256 8-phase main loop (gemm_p8.hpp), one workgroup per CU; the four quadrants of a wave go through the ordinary epilogue
-template <typename T, int FLAGS, int PH> struct P8Pick { typedef GemmP8<T, FLAGS> type; };
-template <typename T, int FLAGS> struct P8Pick<T, FLAGS, 4> { typedef GemmP4<T, FLAGS> type; };
-
-template <typename T, int FLAGS = 0, int PH = 8, int LNF = 0>
+// two-group 256 x 256 main loop (gemm_p8.hpp, bf16), one workgroup per CU; the four quadrants of a wave go through the ordinary epilogue
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void gemm_p8_kernel(const GemmOperands p, const GemmEpilogue e, int a_nrows) {
-    using Tile = typename P8Pick<T, FLAGS, PH>::type;
+    using Tile = GemmP8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int MT = (p.M + Tile::BM - 1) / Tile::BM, cmax = (MT + 7) / 8, NTn = (p.N + Tile::BN - 1) / Tile::BN;
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -377,111 +367,7 @@ void gemm_p8_kernel(const GemmOperands p, const GemmEpilogue e, int a_nrows) {
         m0 = (mstart + ml) * Tile::BM;
         n0 = ntile * Tile::BN;
     }
-    typename Tile::Acc acc;
-    if constexpr ((FLAGS & 32) != 0) {                    // timing experiment (32x32x16 MFMA on the same operand registers): no real output
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[a][b][i][r] = 0.f;
-        Tile::run(p, a_nrows, m0, n0, smem, acc);
-        float t = 0.f;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t += acc[a][b][i][r];
-        if (m0 + (int)threadIdx.x < p.M) reinterpret_cast<float*>(e.C)[(size_t)(m0 + threadIdx.x) * e.ldc + n0] = t;
-    } else {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0, 0, 0, 0};
-        if constexpr (LNF == 2) {
-            // LayerNorm folded into this GEMM with the row statistics its producer left (e.ln_stats; see gemm_dma_kernel): 512 threads = 2 per tile row,
-            // each prefetches half of the row's partials ahead of the main loop; sums, the pair fold and the hand-over through LDS happen after it
-            constexpr int NPRE = 8;
-            const int srow = threadIdx.x >> 1, sq2 = threadIdx.x & 1;
-            const int per = (e.stats_np + 1) / 2, c0 = sq2 * per, c1 = min(c0 + per, e.stats_np);
-            const float2* st = reinterpret_cast<const float2*>(e.ln_stats) + (size_t)min(m0 + srow, p.M - 1) * e.stats_np;
-            float su = 0.f, sq = 0.f;
-            for (int c = c0 + NPRE; c < c1; ++c) { const float2 pr = st[c]; su += pr.x; sq += pr.y; }      // K > 512 only
-            float2 pre[NPRE];
-#pragma unroll
-            for (int u = 0; u < NPRE; ++u) pre[u] = c0 + u < c1 ? st[c0 + u] : float2{0.f, 0.f};
-            Tile::run(p, a_nrows, m0, n0, smem, acc);         // ends with a workgroup barrier: the ring is dead
-#pragma unroll
-            for (int u = 0; u < NPRE; ++u) { su += pre[u].x; sq += pre[u].y; }
-            su += __shfl_xor(su, 1); sq += __shfl_xor(sq, 1);
-            float2* ls = reinterpret_cast<float2*>(smem);
-            if (sq2 == 0) ls[srow] = float2{su, sq};
-            __syncthreads();
-            const int lane = threadIdx.x & 63, wr = threadIdx.x >> 8;
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                float rsum[4], rsq[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { const float2 pr = ls[a * 128 + wr * 64 + i * 16 + (lane & 15)]; rsum[i] = pr.x; rsq[i] = pr.y; }
-                gemm_epilogue<T, 4, 2, 4, true>(acc[a][0], p.M, p.N, e, m0 + a * 128, n0, rsum, rsq, p.K);
-                gemm_epilogue<T, 4, 2, 4, true>(acc[a][1], p.M, p.N, e, m0 + a * 128, n0 + 128, rsum, rsq, p.K);
-            }
-        } else {
-            Tile::run(p, a_nrows, m0, n0, smem, acc);
-            // (four explicit calls: inside a loop over (a, b) hipcc keeps the accumulators in scratch for the epilogue)
-            gemm_epilogue<T, 4, 2, 4>(acc[0][0], p.M, p.N, e, m0, n0);
-            gemm_epilogue<T, 4, 2, 4>(acc[0][1], p.M, p.N, e, m0, n0 + 128);
-            gemm_epilogue<T, 4, 2, 4>(acc[1][0], p.M, p.N, e, m0 + 128, n0);
-            gemm_epilogue<T, 4, 2, 4>(acc[1][1], p.M, p.N, e, m0 + 128, n0 + 128);
-        }
-    }
-}
-
-template <typename T, int FLAGS = 0, int PH = 8, int LNF = 0>
-static int launch_p8(const GemmOperands& p, const GemmEpilogue& e, int a_nrows, hipStream_t s) {
-    using Tile = typename P8Pick<T, FLAGS, PH>::type;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_kernel<T, FLAGS, PH, LNF>), hipFuncAttributeMaxDynamicSharedMemorySize, Tile::SMEM) != hipSuccess) return PK_ELAUNCH;
-        attr_set[dev] = true;
-    }
-    const int MT = (p.M + Tile::BM - 1) / Tile::BM, NT = (p.N + Tile::BN - 1) / Tile::BN;
-    dim3 grid(8 * ((MT + 7) / 8) * NT);
-    GemmOperands pp = p;
-    static const int panel_env = [] { const char* e_ = getenv("PK_GEMM_PANEL"); return e_ ? atoi(e_) : -1; }();
-    pp.panel = panel_env >= 0 ? panel_env : xcd_panel_rows(Tile::BM, p.K, (int)sizeof(T));
-    hipLaunchKernelGGL((gemm_p8_kernel<T, FLAGS, PH, LNF>), grid, dim3(Tile::THREADS), Tile::SMEM, s, pp, e, a_nrows);
-    PK_CHECK_LAUNCH();
-    return PK_OK;
-}
-
-// split-K form of the two-group 256 x 256 loop (bf16; pk_gemm_splitk tile = 2): grid.y slices the contraction exactly like gemm_dma_splitk_kernel; for products whose
-// 256 x 256 tiles are far fewer than the CUs while K is long (the patch-embedding shape 4096 x 512 x 6144: 32 tiles x 8 slices of 12 k-tiles)
-template <typename T>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void gemm_p8_splitk_kernel(GemmOperands p, GemmEpilogue e, int a_nrows, long batch_a, long batch_w, long batch_c) {
-    using Tile = GemmP4<T, 0>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int z = blockIdx.y;
-    p.A = reinterpret_cast<const char*>(p.A) + (size_t)z * batch_a;
-    p.W = reinterpret_cast<const char*>(p.W) + (size_t)z * batch_w;
-    e.C = reinterpret_cast<char*>(e.C) + (size_t)z * batch_c;
-    if (z != 0) e.bias = nullptr;
-    const int MT = (p.M + Tile::BM - 1) / Tile::BM, NTn = (p.N + Tile::BN - 1) / Tile::BN;
-    if ((int)blockIdx.x >= MT * NTn) return;
-    const int m0 = (blockIdx.x % MT) * Tile::BM, n0 = (blockIdx.x / MT) * Tile::BN;
-    typename Tile::Acc acc;
+    Tile::Acc acc;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -491,23 +377,63 @@ void gemm_p8_splitk_kernel(GemmOperands p, GemmEpilogue e, int a_nrows, long bat
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0, 0, 0, 0};
     Tile::run(p, a_nrows, m0, n0, smem, acc);
-    gemm_epilogue<T, 4, 2, 4>(acc[0][0], p.M, p.N, e, m0, n0);
-    gemm_epilogue<T, 4, 2, 4>(acc[0][1], p.M, p.N, e, m0, n0 + 128);
-    gemm_epilogue<T, 4, 2, 4>(acc[1][0], p.M, p.N, e, m0 + 128, n0);
-    gemm_epilogue<T, 4, 2, 4>(acc[1][1], p.M, p.N, e, m0 + 128, n0 + 128);
+    // (four explicit calls: inside a loop over (a, b) hipcc keeps the accumulators in scratch for the epilogue)
+    gemm_epilogue<bf16, 4, 2, 4>(acc[0][0], p.M, p.N, e, m0, n0);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[0][1], p.M, p.N, e, m0, n0 + 128);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[1][0], p.M, p.N, e, m0 + 128, n0);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[1][1], p.M, p.N, e, m0 + 128, n0 + 128);
+}
+
+static int launch_p8(const GemmOperands& p, const GemmEpilogue& e, int a_nrows, hipStream_t s) {
+    using Tile = GemmP8;
+    static LdsOptIn lds;
+    if (lds.raise(reinterpret_cast<const void*>(&gemm_p8_kernel), Tile::SMEM) != PK_OK) return PK_ELAUNCH;
+    const int MT = (p.M + Tile::BM - 1) / Tile::BM, NT = (p.N + Tile::BN - 1) / Tile::BN;
+    dim3 grid(8 * ((MT + 7) / 8) * NT);
+    GemmOperands pp = p;
+    static const int panel_env = [] { const char* e_ = getenv("PK_GEMM_PANEL"); return e_ ? atoi(e_) : -1; }();
+    pp.panel = panel_env >= 0 ? panel_env : xcd_panel_rows(Tile::BM, p.K, (int)sizeof(bf16));
+    hipLaunchKernelGGL(gemm_p8_kernel, grid, dim3(Tile::THREADS), Tile::SMEM, s, pp, e, a_nrows);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+// split-K form of the two-group 256 x 256 loop (bf16; pk_gemm_splitk tile = 2): grid.y slices the contraction exactly like gemm_dma_splitk_kernel; for products whose
+// 256 x 256 tiles are far fewer than the CUs while K is long (the patch-embedding shape 4096 x 512 x 6144: 32 tiles x 8 slices of 12 k-tiles)
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void gemm_p8_splitk_kernel(GemmOperands p, GemmEpilogue e, int a_nrows, long batch_a, long batch_w, long batch_c) {
+    using Tile = GemmP8;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int z = blockIdx.y;
+    p.A = reinterpret_cast<const char*>(p.A) + (size_t)z * batch_a;
+    p.W = reinterpret_cast<const char*>(p.W) + (size_t)z * batch_w;
+    e.C = reinterpret_cast<char*>(e.C) + (size_t)z * batch_c;
+    if (z != 0) e.bias = nullptr;
+    const int MT = (p.M + Tile::BM - 1) / Tile::BM, NTn = (p.N + Tile::BN - 1) / Tile::BN;
+    if ((int)blockIdx.x >= MT * NTn) return;
+    const int m0 = (blockIdx.x % MT) * Tile::BM, n0 = (blockIdx.x / MT) * Tile::BN;
+    Tile::Acc acc;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0, 0, 0, 0};
+    Tile::run(p, a_nrows, m0, n0, smem, acc);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[0][0], p.M, p.N, e, m0, n0);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[0][1], p.M, p.N, e, m0, n0 + 128);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[1][0], p.M, p.N, e, m0 + 128, n0);
+    gemm_epilogue<bf16, 4, 2, 4>(acc[1][1], p.M, p.N, e, m0 + 128, n0 + 128);
 }
 
 static int launch_p8_splitk(const GemmOperands& p, const GemmEpilogue& e, int a_nrows, int splits, long ba, long bw, long bc, hipStream_t s) {
-    using Tile = GemmP4<bf16, 0>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_splitk_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, Tile::SMEM) != hipSuccess) return PK_ELAUNCH;
-        attr_set[dev] = true;
-    }
+    using Tile = GemmP8;
+    static LdsOptIn lds;
+    if (lds.raise(reinterpret_cast<const void*>(&gemm_p8_splitk_kernel), Tile::SMEM) != PK_OK) return PK_ELAUNCH;
     const int MT = (p.M + Tile::BM - 1) / Tile::BM, NT = (p.N + Tile::BN - 1) / Tile::BN;
-    hipLaunchKernelGGL((gemm_p8_splitk_kernel<bf16>), dim3(MT * NT, splits), dim3(Tile::THREADS), Tile::SMEM, s, p, e, a_nrows, ba, bw, bc);
+    hipLaunchKernelGGL(gemm_p8_splitk_kernel, dim3(MT * NT, splits), dim3(Tile::THREADS), Tile::SMEM, s, p, e, a_nrows, ba, bw, bc);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
@@ -600,11 +526,6 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
         if (!dma_ok || !v || !al16(ln_s) || !al16(ln_t) || a_rows) return PK_EINVAL;
         // 128x128 wherever the automatic choice is a large tile (50: the 256x256 loop, which has no folded form)
         const bool big = variant == 24 || variant == 2 || variant == 9 || variant == 50;
-#ifdef PK_P8_ABLATE
-        if (ln_stats && variant == 50 && dtype != 0) {         // the two-group 256 x 256 loop with the producer's row statistics (measured, not used: see below)
-            return dtype == 1 ? launch_p8<bf16, 0, 4, 2>(p, e, a_nrows, s) : launch_p8<bf16x3, 0, 4, 2>(p, e, a_nrows, s);
-        }
-#endif
         if (ln_stats) {
             if (dtype == 1) return big ? launch_dma<bf16, 4, 2, 2, 2, 4, 128, 0, 2>(p, e, a_nrows, s) : launch_dma<bf16, 2, 2, 2, 2, 2, 128, 0, 2>(p, e, a_nrows, s);
             // split-bf16 (round 4): the 4-wave 128x128 tile of that mode (2 threads per row fetch the partials)
@@ -628,33 +549,7 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
             case 24: return launch_dma<bf16, 4, 2, 2, 2, 4>(p, e, a_nrows, s);          // 128x128, 8 waves (2x4), 2 stages (64 KB: 16 waves/CU)
             case 33: return launch_dma<bf16, 2, 2, 3, 2, 2, 128, 2>(p, e, a_nrows, s);  // 64x64, 4 consumers + 2 producers, 3 stages (long K)
             case 27: return launch_dma<bf16, 4, 2, 2, 2, 2>(p, e, a_nrows, s);          // 128x64, 4 waves (wave tile 64x32), 2 stages (48 KB: 3 WG/CU)
-            case 50: return launch_p8<bf16, 0, 4>(p, e, a_nrows, s);                    // 256x256, 8 waves in two groups a barrier apart, 2 phases per k-tile (gemm_p8.hpp), 1 WG/CU
-#ifdef PK_P8_ABLATE
-            // tools/gemm_bench.py ablations behind profiles/gemm_p8_r06.txt (build with PK_EXTRA_HIPCC_FLAGS=-DPK_P8_ABLATE); FLAGS are listed in gemm_p8.hpp
-            case 55: return launch_dma<bf16, 8, 8, 2, 2, 2>(p, e, a_nrows, s);   // ONE wave per SIMD: 256 x 256 tile, 4 waves of 128 x 128 (256 accumulator registers), the plain 2-stage ring
-            case 56: return launch_dma<bf16, 8, 4, 3, 2, 2>(p, e, a_nrows, s);   // 256 x 128, 4 waves of 128 x 64, 3 stages (144 KB)
-            case 60: return launch_p8<bf16, 0, 8>(p, e, a_nrows, s);        // the 8-phase form (16 MFMAs per phase)
-            case 61: return launch_p8<bf16, 1, 8>(p, e, a_nrows, s);
-            case 62: return launch_p8<bf16, 2, 8>(p, e, a_nrows, s);
-            case 63: return launch_p8<bf16, 3, 8>(p, e, a_nrows, s);
-            case 64: return launch_p8<bf16, 4, 8>(p, e, a_nrows, s);
-            case 68: return launch_p8<bf16, 8, 8>(p, e, a_nrows, s);
-            case 70: return launch_p8<bf16, 8, 4>(p, e, a_nrows, s);        // 2-phase form: no s_setprio
-            case 71: return launch_p8<bf16, 1, 4>(p, e, a_nrows, s);        // no in-loop DMA
-            case 72: return launch_p8<bf16, 2, 4>(p, e, a_nrows, s);        // no fragment reads
-            case 73: return launch_p8<bf16, 3, 4>(p, e, a_nrows, s);        // neither: MFMAs + barriers
-            case 74: return launch_p8<bf16, 4, 4>(p, e, a_nrows, s);        // no stagger between the wave groups
-            case 75: return launch_p8<bf16, 64, 4>(p, e, a_nrows, s);       // DMA issued, never waited for (timing only)
-            case 76: return launch_p8<bf16, 128, 4>(p, e, a_nrows, s);      // fragment reads waited for after the barrier
-            case 79: return launch_p8<bf16, 259, 4>(p, e, a_nrows, s);      // MFMAs only: no loads, no barriers
-            case 81: return launch_p8<bf16, 512, 4>(p, e, a_nrows, s);      // DMA 4 + 4 pieces per phase (timing only)
-            case 83: return launch_p8<bf16, 1024, 4>(p, e, a_nrows, s);     // a phase's reads issued before its DMA pieces
-            case 84: return launch_p8<bf16, 2048, 4>(p, e, a_nrows, s);     // half of the DMA pieces issued between the MFMAs
-            case 85: return launch_p8<bf16, 4096 + 64, 4>(p, e, a_nrows, s);   // + 4 ordinary VGPR buffer loads per k-tile between the MFMAs (timing only; vmcnt waits off: the extra loads change the counts)
-            case 88: return launch_p8<bf16, 4096 + 8192 + 64, 4>(p, e, a_nrows, s);   // + 16 of them per k-tile (what a one-wave-per-SIMD design would issue from its MFMA stream)
-            case 86: return launch_p8<bf16, 32, 4>(p, e, a_nrows, s);       // v_mfma_f32_32x32x16_bf16 on the same operand registers (timing only)
-            case 87: return launch_p8<bf16, 35, 4>(p, e, a_nrows, s);       // ... without loads
-#endif
+            case 50: return launch_p8(p, e, a_nrows, s);                               // 256x256, 8 waves in two groups a barrier apart, 2 phases per k-tile (gemm_p8.hpp), 1 WG/CU
             // (round 5: a 256x128 "ping-pong" loop -- one workgroup per CU, two 4-wave groups half an iteration apart, 3-stage 144 KB ring, persistent --
             //  was built, measured and removed: equal to this loop at long K, 13-40 % slower at K = 512; profiles/gemm_pingpong_r05.txt)
             // (256x256 / 256x128 / 128x256 8-wave instantiations were measured again in round 3 against the torch.mm yardstick and removed:
@@ -672,12 +567,6 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
             case 9: return launch_dma<bf16x3, 4, 4, 2>(p, e, a_nrows, s);
             case 24: return launch_dma<bf16x3, 4, 2, 2, 2, 4>(p, e, a_nrows, s);
             case 27: return launch_dma<bf16x3, 4, 2, 2, 2, 2>(p, e, a_nrows, s);
-#ifdef PK_P8_ABLATE
-            // the 256 x 256 two-group loop on the (hi | lo) operand images (gemm_p8.hpp, SPLIT): bit-identical to variant 24, measured in round 6 and NOT used --
-            // split-bf16 is bound by its three MFMAs per product, not by the fill: 8192^3 390 vs 352 TF-equivalent, FF1 at 9216 rows 111 vs 104 us, at 4608 rows
-            // 107 vs 61 us (profiles/gemm_p8_r06.txt)
-            case 50: return launch_p8<bf16x3, 0, 4>(p, e, a_nrows, s);
-#endif
             default: return PK_EINVAL;
         }
     }

@@ -651,13 +651,8 @@ extern "C" int pk_patch_embed(const float* video, int B, int C, int F, int H, in
     const bool wide = tn_env ? tn_env == 4 : N >= 128;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (wide) {
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
-        if (!attr_set[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_embed_kernel_n128), hipFuncAttributeMaxDynamicSharedMemorySize, PeGeom<4>::SMEM) != hipSuccess) return PK_ELAUNCH;
-            attr_set[dev] = true;
-        }
+        static pk::LdsOptIn lds;
+        if (lds.raise(reinterpret_cast<const void*>(&patch_embed_kernel_n128), PeGeom<4>::SMEM) != PK_OK) return PK_ELAUNCH;
         const int NT = (N + PeGeom<4>::BN - 1) / PeGeom<4>::BN;
         hipLaunchKernelGGL(patch_embed_kernel_n128, dim3(8 * ((MT + 7) / 8) * NT), dim3(64 * PE_WAVES), PeGeom<4>::SMEM, st, a);
     } else {
@@ -706,13 +701,8 @@ extern "C" int pk_patch_embed_splitk(const float* video, int B, int C, int F, in
         work += G.mtiles * G.nslices;
     }
     if (ngroups == 1) a.g[1] = a.g[0];
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_embed_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PW_SMEM) != hipSuccess) return PK_ELAUNCH;
-        attr_set[dev] = true;
-    }
+    static pk::LdsOptIn lds;
+    if (lds.raise(reinterpret_cast<const void*>(&patch_embed_wide_kernel), PW_SMEM) != PK_OK) return PK_ELAUNCH;
     hipLaunchKernelGGL(patch_embed_wide_kernel, dim3(8 * ((work + 7) / 8)), dim3(64 * PE_WAVES), PW_SMEM, reinterpret_cast<hipStream_t>(stream), a);
     PK_CHECK_LAUNCH();
     return PK_OK;

@@ -749,16 +749,10 @@ static int vocab_sample_launch(int dtype, const void* A, int lda, const void* W,
     if (dtype == 1 && resident_env && D == 64 * VR_NT && M >= (resident_env == 3 ? 2048 : 1024)) {
         const bool lse = e.need_lse != 0;
         const int vi = (parity ? 2 : 0) + (lse ? 1 : 0);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return PK_ELAUNCH;
         const dim3 rgrid(256);                                         // 8 XCDs x 32 CUs: one workgroup per CU
 #define PK_VR(NWV, RNG, FA, TW, PAR, LS) do { \
-            static bool attr_set[64] = {}; \
-            if (!attr_set[dev]) { \
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&vocab_resident_kernel<NWV, RNG, FA, TW, PAR, LS>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, VR_SMEM) != hipSuccess) return PK_ELAUNCH; \
-                attr_set[dev] = true; \
-            } \
+            static pk::LdsOptIn lds; \
+            if (lds.raise(reinterpret_cast<const void*>(&vocab_resident_kernel<NWV, RNG, FA, TW, PAR, LS>), VR_SMEM) != PK_OK) return PK_ELAUNCH; \
             hipLaunchKernelGGL((vocab_resident_kernel<NWV, RNG, FA, TW, PAR, LS>), rgrid, dim3(64 * NWV), VR_SMEM, s, p, e); } while (0)
         if (resident_env == 2 || (resident_env == 3 && !lse)) {
             switch (vi) { case 0: PK_VR(12, 4, false, 1, false, false); break; case 1: PK_VR(12, 4, false, 1, false, true); break;

@@ -725,50 +725,51 @@ def test_training_loop_tracks_torch_adamw_on_the_oracle(dtype):
 
 @pytest.mark.parametrize('dtype,tol', [('fp32', 1e-5), ('bf16x3', 2e-4), ('bf16', 2e-2)])
 def test_gemm_splitk_matches_plain_product(dtype, tol):
-    """pk_gemm_splitk + pk_sum_batch (the weight-gradient product of the training step) against an f64 product, ragged M / N tiles"""
+    """pk_gemm_splitk + pk_sum_batch (the weight-gradient product of the training step) against an f64 product, ragged M / N tiles, two row counts"""
     from phenaki_pytorch_amd import _lib as L
     from phenaki_pytorch_amd.attention import resolve_dtype
     from phenaki_pytorch_amd.train import pack_operand, _weight_grad_gemm
     dt = resolve_dtype(dtype)
     g = torch.Generator().manual_seed(31)
-    rows, N, K = 1000, 200, 136                     # dW (N, K) = dy^T (N, rows) x (rows, K)
-    dy, x = torch.randn(rows, N, generator=g), torch.randn(rows, K, generator=g)
-    want = (dy.double().t() @ x.double()).float()
-    q = 64 if dtype == 'bf16' else 32
-    Mp = (rows + q - 1) // q * q
-    dyT = pack_operand(dy.cuda(), dt, transpose=True, side='a')
-    xT = pack_operand(x.cuda(), dt, transpose=True)
-    for splits in (2, 4):
-        if Mp % (splits * q):
-            continue
-        part = torch.empty((splits, N * K), device='cuda')
-        L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part)
-        out = torch.empty((N, K), device='cuda')
-        L.sum_batch(part, splits, out, N * K)
-        close(out.cpu(), want, tol, f'split-K x{splits} ({dtype})')
-    out2 = torch.empty((N, K), device='cuda')
-    _weight_grad_gemm(dt, dyT, xT, N, K, Mp, out2)
-    close(out2.cpu(), want, tol, f'weight-gradient product ({dtype})')
-    # round 4: 128 x 128 tiles and a bias carried by slice 0 (the split-bf16 patch-embedding product)
-    bias = torch.randn(K, generator=g)
-    for splits in (2, 4):
-        if Mp % (splits * q):
-            continue
-        part = torch.full((splits, N * K), float('nan'), device='cuda')
-        L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part, bias=bias.cuda(), tile=1)
-        out = torch.empty((N, K), device='cuda')
-        L.sum_batch(part, splits, out, N * K)
-        close(out.cpu(), want + bias, tol, f'split-K x{splits}, 128-wide tiles + bias ({dtype})')
-    # round 6: 256 x 256 tiles on the two-group loop (bf16 only; the other operand types are refused)
-    for splits in (2, 4):
-        if Mp % (splits * q):
-            continue
-        part = torch.full((splits, N * K), float('nan'), device='cuda')
-        if dtype != 'bf16':
-            with pytest.raises(RuntimeError):
-                L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part, tile=2)
-            break
-        L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part, bias=bias.cuda(), tile=2)
-        out = torch.empty((N, K), device='cuda')
-        L.sum_batch(part, splits, out, N * K)
-        close(out.cpu(), want + bias, tol, f'split-K x{splits}, 256-wide tiles + bias ({dtype})')
+    N, K = 200, 136                                 # dW (N, K) = dy^T (N, rows) x (rows, K)
+    for rows in (1000, 380):                        # 380: Mp = 384, i.e. 2 slices of 192 = 3 k-tiles each in bf16 (an odd count above one)
+        dy, x = torch.randn(rows, N, generator=g), torch.randn(rows, K, generator=g)
+        want = (dy.double().t() @ x.double()).float()
+        q = 64 if dtype == 'bf16' else 32
+        Mp = (rows + q - 1) // q * q
+        dyT = pack_operand(dy.cuda(), dt, transpose=True, side='a')
+        xT = pack_operand(x.cuda(), dt, transpose=True)
+        for splits in (2, 4):
+            if Mp % (splits * q):
+                continue
+            part = torch.empty((splits, N * K), device='cuda')
+            L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part)
+            out = torch.empty((N, K), device='cuda')
+            L.sum_batch(part, splits, out, N * K)
+            close(out.cpu(), want, tol, f'split-K x{splits} ({dtype}, rows {rows})')
+        out2 = torch.empty((N, K), device='cuda')
+        _weight_grad_gemm(dt, dyT, xT, N, K, Mp, out2)
+        close(out2.cpu(), want, tol, f'weight-gradient product ({dtype}, rows {rows})')
+        # round 4: 128 x 128 tiles and a bias carried by slice 0 (the split-bf16 patch-embedding product)
+        bias = torch.randn(K, generator=g)
+        for splits in (2, 4):
+            if Mp % (splits * q):
+                continue
+            part = torch.full((splits, N * K), float('nan'), device='cuda')
+            L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part, bias=bias.cuda(), tile=1)
+            out = torch.empty((N, K), device='cuda')
+            L.sum_batch(part, splits, out, N * K)
+            close(out.cpu(), want + bias, tol, f'split-K x{splits}, 128-wide tiles + bias ({dtype}, rows {rows})')
+        # round 6: 256 x 256 tiles on the two-group loop (bf16 only; the other operand types are refused)
+        for splits in (2, 4):
+            if Mp % (splits * q):
+                continue
+            part = torch.full((splits, N * K), float('nan'), device='cuda')
+            if dtype != 'bf16':
+                with pytest.raises(RuntimeError):
+                    L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part, tile=2)
+                break
+            L.gemm_splitk(dt, dyT, xT, N, K, Mp, splits, part, bias=bias.cuda(), tile=2)
+            out = torch.empty((N, K), device='cuda')
+            L.sum_batch(part, splits, out, N * K)
+            close(out.cpu(), want + bias, tol, f'split-K x{splits}, 256-wide tiles + bias ({dtype}, rows {rows})')

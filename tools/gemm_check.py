@@ -1,5 +1,5 @@
 """Quick parity check of experimental pk_gemm main-loop variants against variant 24 (the 128 x 128 LDS-DMA loop) and an f64 reference:
-    python tools/gemm_check.py 50,70 [--reps 3]
+    python tools/gemm_check.py 50 [--reps 3]        (50: the 256 x 256 two-group loop, bf16 only; with --x3 e.g. 9,27)
 Shapes cover M / N / K tails, 1 / 2 / odd numbers of k-tiles, and a multi-round grid (race screen: repeated, compared bit for bit)."""
 import sys
 import torch
