@@ -42,6 +42,9 @@ def main():
     ap.add_argument('--folder', default='', help='directory of GIFs to train on (VideoDataset); default: synthetic videos')
     ap.add_argument('--gif', default='', help='write the reconstruction of the last batch here')
     ap.add_argument('--save', default='')
+    ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm inside the AdamW update (cvivit_trainer.py:245-246)')
+    ap.add_argument('--discr-max-grad-norm', type=float, default=None, help='the same for the discriminator optimizer of --gan (cvivit_trainer.py:268-269)')
+    ap.add_argument('--ema', action='store_true', help='keep an exponential moving average of the tokenizer (cvivit_trainer.py:93, 282); saved as <save>.ema.pt')
     ap.add_argument('--gan', action='store_true', help='train with the perceptual + adversarial objective and a discriminator step')
     ap.add_argument('--gp-every', type=int, default=4, help='apply the gradient penalty every this many steps (cvivit_trainer.py:224)')
     args = ap.parse_args()
@@ -59,11 +62,12 @@ def main():
     P.set_compute_dtype(cvivit, args.dtype)
     # the reference keeps two optimizers: the tokenizer's parameters (everything but discr.*) and the discriminator's (cvivit_trainer.py:118-124)
     params = [p for n, p in cvivit.named_parameters() if p.requires_grad and not n.startswith('discr.')]
-    opt = P.get_optimizer(params, lr=3e-4, wd=0.)
+    opt = P.get_optimizer(params, lr=3e-4, wd=0., max_grad_norm=args.max_grad_norm)
     discr_params = list(cvivit.discr.parameters()) if args.gan else []
-    discr_opt = P.get_optimizer(discr_params, lr=3e-4, wd=0.) if args.gan else None
+    discr_opt = P.get_optimizer(discr_params, lr=3e-4, wd=0., max_grad_norm=args.discr_max_grad_norm) if args.gan else None
     reducer = P.GradientReducer(params, buffers=list(cvivit.buffers())) if ws > 1 else None     # broadcasts rank 0's parameters, as DDP does at wrap time
     discr_reducer = P.GradientReducer(discr_params) if (ws > 1 and args.gan) else None
+    ema = P.EMA(cvivit, update_after_step=min(100, args.steps // 2), update_every=10 if args.steps > 40 else 1) if (args.ema and rank == 0) else None
     torch.manual_seed(1 + rank)            # from here on (data order, frame masks) every rank draws its own stream
 
     if args.folder:
@@ -101,6 +105,8 @@ def main():
             if discr_reducer is not None:
                 discr_reducer.finish()
             discr_opt.step()
+        if ema is not None:
+            ema.update()                                               # after the step's optimizer updates (cvivit_trainer.py:282)
         if rank == 0 and (step % 5 == 0 or step == args.steps - 1):
             tail = f'  discriminator loss {float(discr_loss.detach()):.5f}' if discr_loss is not None else ''
             print(f'step {step:4d}  {"vae" if args.gan else "reconstruction"} loss {float(loss.detach()):.5f}{tail}', flush=True)
@@ -115,6 +121,8 @@ def main():
         print('wrote', args.gif)
     if rank == 0 and args.save:
         torch.save(cvivit.state_dict(), args.save)
+        if ema is not None:
+            torch.save(ema.state_dict(), args.save + '.ema.pt')
     if ws > 1:
         dist.destroy_process_group()
 

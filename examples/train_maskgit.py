@@ -24,6 +24,7 @@ def main():
     ap.add_argument('--small', action='store_true', help='a small geometry (dim 128, 64 x 64 pixels) instead of the BASELINE one')
     ap.add_argument('--attn-dropout', type=float, default=0., help='dropout on the attention probabilities of MaskGit and the critic (in training mode)')
     ap.add_argument('--ff-dropout', type=float, default=0., help='dropout behind GEGLU in their feed-forwards')
+    ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm inside the AdamW update (phenaki_trainer.py:380-381)')
     ap.add_argument('--save', default='')
     args = ap.parse_args()
     ws = int(os.environ.get('WORLD_SIZE', '1'))
@@ -43,7 +44,7 @@ def main():
     phenaki = P.Phenaki(cvivit=cvivit, maskgit=maskgit, critic=critic, text_embed_dim=ctx_dim).cuda()
     P.set_compute_dtype(phenaki, args.dtype)
     params = list(maskgit.parameters()) + list(critic.parameters())
-    opt = P.get_optimizer(params, lr=1e-4, wd=1e-2)
+    opt = P.get_optimizer(params, lr=1e-4, wd=1e-2, max_grad_norm=args.max_grad_norm)
 
     if ws > 1:
         P.broadcast_module(phenaki)        # every replica starts from rank 0's weights and buffers (what accelerate / DDP do at wrap time)
@@ -65,7 +66,8 @@ def main():
             reducer.finish()                                                     # the buckets were all-reduced while backward ran (dist.py)
         opt.step()
         if step % 5 == 0 or step == args.steps - 1:
-            print(f'step {step:4d}  loss {float(loss.detach()):.4f}', flush=True)
+            norm = f'  grad norm {float(opt.last_grad_norm):.4f}' if opt.last_grad_norm is not None else ''
+            print(f'step {step:4d}  loss {float(loss.detach()):.4f}{norm}', flush=True)
     torch.cuda.synchronize()
     if t0 is not None and args.steps > 3:
         dt = (time.perf_counter() - t0) / (args.steps - 3)

@@ -474,6 +474,24 @@ int pk_adamw(float* p, const float* g, float* m, float* v, float lr, float beta1
 /* the same update for `count` tensors sharing hyper-parameters and step in a handful of launches: table = HOST array of count x 5 64-bit
  * words {p, g, m, v, numel} (device pointers of contiguous f32 tensors).  Bit-identical to per-tensor pk_adamw calls. */
 int pk_adamw_multi(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step, void* stream);
+/* the tail of a training step (reference cvivit_trainer.py:245-246, 268-269, 282; phenaki_trainer.py:380-381): global-norm gradient clipping and the
+ * exponential moving average of a model's weights.  Tables are HOST arrays of 64-bit words, device pointers of contiguous f32 tensors, numel > 0;
+ * the launches are packed as pk_adamw_multi packs them.  No atomics: no result depends on launch order or block scheduling.
+ * pk_grad_sumsq_parts: the number of f32 partial sums pk_grad_sumsq writes for a table of count x {g, numel} (host only; < 0: an error code).
+ * pk_grad_sumsq: partials[b] = the sum of squares of one fixed chunk of one gradient; nparts must be what pk_grad_sumsq_parts returned.
+ * pk_grad_clip_coef: out[0] = total_norm = sqrt(the partials summed in index order, in double), out[1] = min(max_norm / (total_norm + 1e-6), 1)
+ * in f32 -- the values of torch.nn.utils.clip_grad_norm_(norm_type = 2, error_if_nonfinite = False): a NaN norm gives a NaN coefficient.
+ * pk_scale_multi: g = g * *coef_dev in place (one rounded multiply), the coefficient read from device memory.
+ * pk_adamw_multi_scaled: pk_adamw_multi with every gradient element read as g * *gscale_dev (one rounded multiply): bit-identical to
+ * pk_scale_multi followed by pk_adamw_multi, without writing the gradients.
+ * pk_ema_multi: table of count x {ema, src, numel}; ema = ema + weight (src - ema); weight >= 1 stores src verbatim (an exact copy). */
+int pk_grad_sumsq_parts(const long long* table, int count);
+int pk_grad_sumsq(const long long* table, int count, float* partials, long long nparts, void* stream);
+int pk_grad_clip_coef(const float* partials, long long nparts, float max_norm, float* out, void* stream);
+int pk_scale_multi(const long long* table, int count, const float* coef_dev, void* stream);
+int pk_adamw_multi_scaled(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step,
+                          const float* gscale_dev, void* stream);
+int pk_ema_multi(const long long* table, int count, float weight, void* stream);
 /* attention backward (attention.py:132-182).  pk_attn_train_prep: the f32 operands q^ = l2norm(q) q_scale scale -> Qh (S heads, n, 64),
  * k^ = l2norm([null_k ; k]) k_scale -> Kh, [null_v ; v] -> Vh (S heads, nnull + n_kv, 64) from the projection outputs q (S n, ldq), kv (S n_kv, ldkv).
  * pk_attn_bwd_ws: dQh / dKh / dVh from those, the forward output O (f32 or bf16) and dO; bias (heads, n, n_kv) / kmask (S, n_kv) cover the real keys;

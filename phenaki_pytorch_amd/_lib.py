@@ -111,6 +111,12 @@ SIGNATURES = {
     'pk_gemm_splitk': [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P],
     'pk_adamw': [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _LL, _P],
     'pk_adamw_multi': [_P, _I, _F, _F, _F, _F, _F, _I, _P],
+    'pk_grad_sumsq_parts': [_P, _I],
+    'pk_grad_sumsq': [_P, _I, _P, _LL, _P],
+    'pk_grad_clip_coef': [_P, _LL, _F, _P, _P],
+    'pk_scale_multi': [_P, _I, _P, _P],
+    'pk_adamw_multi_scaled': [_P, _I, _F, _F, _F, _F, _F, _I, _P, _P],
+    'pk_ema_multi': [_P, _I, _F, _P],
     'pk_attn_bwd_ws': [_P, _P, _P, _P, _LL, _I, _P, _LL, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _LL, _P, _P],
     'pk_attn_bwd_work': [_I, _I, _I, _I, _I],
     'pk_im2col': [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _LL, _P],
@@ -904,6 +910,58 @@ def adamw_multi(entries, lr, beta1, beta2, eps, wd, step, device):
     rc = load().pk_adamw_multi(table.ctypes.data, len(entries), float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step),
                                torch.cuda.current_stream(device).cuda_stream)
     _check(rc, 'pk_adamw_multi')
+
+
+def adamw_multi_scaled(entries, lr, beta1, beta2, eps, wd, step, gscale, device):
+    """adamw_multi on gradients read as g * gscale[0] (gscale: f32 device tensor, the coefficient grad_norm_coef left there)"""
+    import numpy as np
+    table = np.empty((len(entries), 5), dtype=np.int64)
+    for i, (p, g, m, v) in enumerate(entries):
+        table[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
+    rc = load().pk_adamw_multi_scaled(table.ctypes.data, len(entries), float(lr), float(beta1), float(beta2), float(eps), float(wd), int(step),
+                                      gscale.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+    _check(rc, 'pk_adamw_multi_scaled')
+
+
+def _grad_table(grads):
+    import numpy as np
+    table = np.empty((len(grads), 2), dtype=np.int64)
+    for i, g in enumerate(grads):
+        table[i] = (g.data_ptr(), g.numel())
+    return table
+
+
+_norm_partials = {}                                    # device index -> f32 workspace of the norm pass, grown when needed
+
+
+def grad_norm_coef(grads, max_norm, device):
+    """grads: non-empty contiguous f32 tensors on `device` -> (table, out): out (2,) f32 = {global L2 norm, min(max_norm / (norm + 1e-6), 1)},
+    left on the device (no synchronisation); table is the {g, numel} host table for scale_multi"""
+    table = _grad_table(grads)
+    lib, s = load(), torch.cuda.current_stream(device).cuda_stream
+    nparts = lib.pk_grad_sumsq_parts(table.ctypes.data, len(grads))
+    if nparts < 0:
+        _check(nparts, 'pk_grad_sumsq_parts')
+    work = _norm_partials.get(device.index)
+    if work is None or work.numel() < nparts:
+        work = _norm_partials[device.index] = torch.empty((nparts,), device=device, dtype=torch.float32)
+    out = torch.empty((2,), device=device, dtype=torch.float32)
+    _check(lib.pk_grad_sumsq(table.ctypes.data, len(grads), work.data_ptr(), nparts, s), 'pk_grad_sumsq')
+    _check(lib.pk_grad_clip_coef(work.data_ptr(), nparts, float(max_norm), out.data_ptr(), s), 'pk_grad_clip_coef')
+    return table, out
+
+
+def scale_multi(table, coef, device):
+    _check(load().pk_scale_multi(table.ctypes.data, table.shape[0], coef.data_ptr(), torch.cuda.current_stream(device).cuda_stream), 'pk_scale_multi')
+
+
+def ema_multi(pairs, weight, device):
+    """pairs: list of (ema, src) contiguous f32 device tensors of equal, non-zero numel: ema += weight (src - ema); weight >= 1 copies"""
+    import numpy as np
+    table = np.empty((len(pairs), 3), dtype=np.int64)
+    for i, (e, x) in enumerate(pairs):
+        table[i] = (e.data_ptr(), x.data_ptr(), e.numel())
+    _check(load().pk_ema_multi(table.ctypes.data, len(pairs), float(weight), torch.cuda.current_stream(device).cuda_stream), 'pk_ema_multi')
 
 
 def gemm_splitk(dtype, A, W, M, N, K, splits, C, bias=None, tile=0):

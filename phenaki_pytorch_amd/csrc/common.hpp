@@ -191,6 +191,16 @@ __device__ __forceinline__ long xcd_contiguous_block(unsigned b, unsigned nblock
 __host__ __device__ inline unsigned xcd_padded_grid(long nblocks) { return (unsigned)(8 * ((nblocks + 7) / 8)); }
 
 // ---- wave reductions (64 lanes) ----------------------------------------------------------
+// a product / sum rounded to f32 on its own: never contracted into an fma with a neighbouring operation (the toolchain's __fmul_rn is a plain
+// `x * y`, which -ffp-contract=fast may fuse)
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

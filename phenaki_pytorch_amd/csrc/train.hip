@@ -644,16 +644,46 @@ __global__ __launch_bounds__(256) void bce_head_kernel(const float* __restrict__
 // m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p = p (1 - lr wd) - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // (round 6: a 16-bytes-per-lane form of this kernel measured 10.7 vs 10.2 us per launch -- the 4-byte form already streams the step's 4.3 GB at the rate the
 // part sustains for 7 interleaved streams; removed)
+// SCALED: every gradient element is read as g[i] * *scale rounded on its own (mul_rn) -- the clip coefficient pk_grad_clip_coef left on the device; the
+// separately rounded multiply cannot be contracted into the moment updates, so the result is bit-identical to pk_scale_multi followed by the unscaled
+// kernel.  The pointer is a parameter pack of SCALED entries: the unscaled instantiations keep the parameter list, the kernel-argument layout and
+// the instructions they had before the template.
+__device__ __forceinline__ float grad_scale() { return 1.0f; }
+__device__ __forceinline__ float grad_scale(const float* s) { return s[0]; }
+// one element of the SCALED update.  Which products the compiler fuses into an fma and which it rounds on their own is its choice per
+// instantiation (-ffp-contract=fast), and with a scaled gradient it chose differently for the first moment.  The unscaled kernels keep the source
+// they have always had (their instructions do not change); this form spells out, rounding by rounding, what that source compiles to -- m as
+// fma(b1, m, (1 - b1) g), v and p as separately rounded products and sums, the denominator and 1 - lr wd as one fma each -- so that the two agree
+// bit for bit (tests/test_step_tail_gpu.py holds them to it)
+__device__ __forceinline__ void adamw_scaled_element(float* __restrict__ p, float g, float* __restrict__ m, float* __restrict__ v, float gs,
+                                                     float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2) {
+    const float gi = mul_rn(g, gs);
+    const float mi = fmaf(b1, *m, mul_rn(1.0f - b1, gi));
+    const float vi = add_rn(mul_rn(b2, *v), mul_rn(mul_rn(1.0f - b2, gi), gi));
+    *m = mi;
+    *v = vi;
+    const float denom = fmaf(sqrtf(vi), rsqrt_bc2, eps);
+    *p = add_rn(mul_rn(*p, fmaf(-lr, wd, 1.0f)), -mul_rn(lr / bc1, mi / denom));
+}
+
+template <bool SCALED, class... GS>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2, long n) {
+                                                    float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2, long n,
+                                                    GS... sc) {
+    static_assert(sizeof...(GS) == (SCALED ? 1 : 0), "one scale pointer when SCALED, none otherwise");
+    const float gs = grad_scale(sc...);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-        p[i] = p[i] * (1.0f - lr * wd) - (lr / bc1) * (mi / denom);
+        if constexpr (SCALED) {
+            adamw_scaled_element(p + i, g[i], m + i, v + i, gs, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
+        } else {
+            const float gi = g[i];
+            const float mi = b1 * m[i] + (1.0f - b1) * gi;
+            const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+            m[i] = mi;
+            v[i] = vi;
+            const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
+            p[i] = p[i] * (1.0f - lr * wd) - (lr / bc1) * (mi / denom);
+        }
     }
 }
 
@@ -666,7 +696,10 @@ struct AdamMulti {
     unsigned short bc[ADAM_B];
     unsigned char bt[ADAM_B];
 };
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamMulti a, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2) {
+template <bool SCALED, class... GS>
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamMulti a, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
+                                                          GS... sc) {
+    const float gs = grad_scale(sc...);
     const int t = a.bt[blockIdx.x];
     const long base = (long)a.bc[blockIdx.x] * ADAM_CHUNK;
     float* __restrict__ p = a.p[t];
@@ -678,13 +711,17 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamMulti a, flo
     for (int u = 0; u < ADAM_CHUNK / 256; ++u) {
         const long i = base + u * 256 + threadIdx.x;
         if (i >= n) break;
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-        p[i] = p[i] * (1.0f - lr * wd) - (lr / bc1) * (mi / denom);
+        if constexpr (SCALED) {
+            adamw_scaled_element(p + i, g[i], m + i, v + i, gs, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
+        } else {
+            const float gi = g[i];
+            const float mi = b1 * m[i] + (1.0f - b1) * gi;
+            const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+            m[i] = mi;
+            v[i] = vi;
+            const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
+            p[i] = p[i] * (1.0f - lr * wd) - (lr / bc1) * (mi / denom);
+        }
     }
 }
 
@@ -697,7 +734,10 @@ struct AdamBig {
     long n[ADAM_BIG_T];
     int blk0[ADAM_BIG_T];
 };
-__global__ __launch_bounds__(256) void adamw_big_kernel(const AdamBig a, int count, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2) {
+template <bool SCALED, class... GS>
+__global__ __launch_bounds__(256) void adamw_big_kernel(const AdamBig a, int count, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
+                                                        GS... sc) {
+    const float gs = grad_scale(sc...);
     const int b = blockIdx.x;
     int t = 0;
 #pragma unroll
@@ -712,13 +752,17 @@ __global__ __launch_bounds__(256) void adamw_big_kernel(const AdamBig a, int cou
     for (int u = 0; u < ADAM_BIG_CHUNK / 256; ++u) {
         const long i = base + u * 256 + threadIdx.x;
         if (i >= n) break;
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-        p[i] = p[i] * (1.0f - lr * wd) - (lr / bc1) * (mi / denom);
+        if constexpr (SCALED) {
+            adamw_scaled_element(p + i, g[i], m + i, v + i, gs, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
+        } else {
+            const float gi = g[i];
+            const float mi = b1 * m[i] + (1.0f - b1) * gi;
+            const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+            m[i] = mi;
+            v[i] = vi;
+            const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
+            p[i] = p[i] * (1.0f - lr * wd) - (lr / bc1) * (mi / denom);
+        }
     }
 }
 
@@ -1047,14 +1091,15 @@ extern "C" int pk_bce_head(const float* e, long lde, const float* w, const float
 // the same update for `count` tensors of one hyper-parameter set and step: table[i] = {p, g, m, v, n} (HOST array of 5 x 64-bit words per tensor).
 // Tensors of >= 256 Ki elements get their own launch (bandwidth-bound anyway); the small ones -- a transformer has hundreds: LayerNorm
 // gains, biases, scales, position-MLP layers -- are packed ADAM_T tensors / ADAM_B blocks per launch (256 per-tensor launches -> ~10).
-extern "C" int pk_adamw_multi(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step, void* stream) {
+template <bool SCALED, class... GS>
+static int adamw_multi(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step, void* stream, GS... sc) {
     if (!table || count <= 0 || step <= 0) return PK_EINVAL;
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step), rs = 1.0f / sqrtf(bc2);
     hipStream_t s = STREAM(stream);
     AdamMulti a;
     int nt = 0, nb = 0;
     auto flush = [&]() {
-        if (nb > 0) hipLaunchKernelGGL(adamw_multi_kernel, dim3(nb), dim3(256), 0, s, a, lr, beta1, beta2, eps, wd, bc1, rs);
+        if (nb > 0) hipLaunchKernelGGL(adamw_multi_kernel<SCALED>, dim3(nb), dim3(256), 0, s, a, lr, beta1, beta2, eps, wd, bc1, rs, sc...);
         nt = 0; nb = 0;
     };
     // large tensors: up to ADAM_BIG_T per launch (A/B switch PK_ADAMW_BIG=0: one launch per tensor, the round-3 form)
@@ -1063,7 +1108,7 @@ extern "C" int pk_adamw_multi(const long long* table, int count, float lr, float
     int bt = 0;
     long bblocks = 0;
     auto flush_big = [&]() {
-        if (bt > 0) hipLaunchKernelGGL(adamw_big_kernel, dim3((unsigned)bblocks), dim3(256), 0, s, big, bt, lr, beta1, beta2, eps, wd, bc1, rs);
+        if (bt > 0) hipLaunchKernelGGL(adamw_big_kernel<SCALED>, dim3((unsigned)bblocks), dim3(256), 0, s, big, bt, lr, beta1, beta2, eps, wd, bc1, rs, sc...);
         bt = 0; bblocks = 0;
     };
     for (int i = 0; i < count; ++i) {
@@ -1076,7 +1121,7 @@ extern "C" int pk_adamw_multi(const long long* table, int count, float lr, float
         if (!p || !g || !m || !v || n <= 0) return PK_EINVAL;
         if (n >= 262144) {
             if (!big_multi) {
-                hipLaunchKernelGGL(adamw_kernel, dim3(nblocks(n)), dim3(256), 0, s, p, g, m, v, lr, beta1, beta2, eps, wd, bc1, rs, n);
+                hipLaunchKernelGGL(adamw_kernel<SCALED>, dim3(nblocks(n)), dim3(256), 0, s, p, g, m, v, lr, beta1, beta2, eps, wd, bc1, rs, n, sc...);
                 continue;
             }
             const long nbk = (n + ADAM_BIG_CHUNK - 1) / ADAM_BIG_CHUNK;
@@ -1101,11 +1146,22 @@ extern "C" int pk_adamw_multi(const long long* table, int count, float lr, float
     return PK_OK;
 }
 
+extern "C" int pk_adamw_multi(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step, void* stream) {
+    return adamw_multi<false>(table, count, lr, beta1, beta2, eps, wd, step, stream);
+}
+
+// pk_adamw_multi on gradients read as __fmul_rn(g, *gscale_dev): the clipped update without the extra read and write of every gradient
+extern "C" int pk_adamw_multi_scaled(const long long* table, int count, float lr, float beta1, float beta2, float eps, float wd, int step,
+                                     const float* gscale_dev, void* stream) {
+    if (!gscale_dev) return PK_EINVAL;
+    return adamw_multi<true>(table, count, lr, beta1, beta2, eps, wd, step, stream, gscale_dev);
+}
+
 // step = 1, 2, ...: the number of this update (bias corrections 1 - beta^step); wd = 0: plain Adam
 extern "C" int pk_adamw(float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2, float eps, float wd, int step, long n, void* stream) {
     if (!p || !g || !m || !v || n <= 0 || step <= 0) return PK_EINVAL;
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(nblocks(n)), dim3(256), 0, STREAM(stream), p, g, m, v, lr, beta1, beta2, eps, wd, bc1, 1.0f / sqrtf(bc2), n);
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(nblocks(n)), dim3(256), 0, STREAM(stream), p, g, m, v, lr, beta1, beta2, eps, wd, bc1, 1.0f / sqrtf(bc2), n);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
