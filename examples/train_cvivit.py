@@ -1,13 +1,15 @@
 """The training step of the reference's CViViTTrainer (cvivit_trainer.py:226-270) on the MI355X kernels.  Default: the generator step without
 the GAN terms -- zero_grad -> CViViT.forward (reconstruction MSE through the straight-through LFQ) -> backward -> [gradient all-reduce] -> AdamW.
 `--gan`: both halves of train_step -- the generator objective recon + perceptual + adaptive_weight * hinge generator loss (cvivit.py:585-671; the
-perceptual network is whatever module is passed as `vgg=`, here a small stand-in because torchvision's VGG16 cannot be downloaded offline), then the
+perceptual network is whatever module is passed as `vgg=`: by default a small stand-in, because torchvision's pretrained VGG16 cannot be downloaded
+offline; `--vgg16 PATH` loads a torchvision vgg16 state dict into P.VGG16Features, the reference's network on this library's kernels), then the
 discriminator's hinge loss with the gradient penalty every `--gp-every`-th step (cvivit_trainer.py:224, 251-270).  Finally the
 reconstruction of one batch is written as a GIF (data.py:103-113).  `--folder` trains on the GIFs of a directory through VideoDataset /
 DataLoader (data.py:177-265); without it synthetic videos stand in.  One process per GPU (`torchrun --nproc-per-node N ...`).
 
     python examples/train_cvivit.py --steps 20 --small --gif /tmp/recon.gif
     python examples/train_cvivit.py --steps 20 --small --gan
+    python examples/train_cvivit.py --steps 20 --gan --vgg16 vgg16.pt
 """
 import argparse
 import contextlib
@@ -46,6 +48,8 @@ def main():
     ap.add_argument('--discr-max-grad-norm', type=float, default=None, help='the same for the discriminator optimizer of --gan (cvivit_trainer.py:268-269)')
     ap.add_argument('--ema', action='store_true', help='keep an exponential moving average of the tokenizer (cvivit_trainer.py:93, 282); saved as <save>.ema.pt')
     ap.add_argument('--gan', action='store_true', help='train with the perceptual + adversarial objective and a discriminator step')
+    ap.add_argument('--vgg16', default='', metavar='PATH', help='with --gan: a torchvision vgg16 state dict (torch.save(vgg16.state_dict(), PATH)); the '
+                    'perceptual network is then the real VGG16 (P.VGG16Features) instead of the stand-in')
     ap.add_argument('--gp-every', type=int, default=4, help='apply the gradient penalty every this many steps (cvivit_trainer.py:224)')
     args = ap.parse_args()
     ws = int(os.environ.get('WORLD_SIZE', '1'))
@@ -56,9 +60,15 @@ def main():
     torch.manual_seed(1)                   # the model is built under a rank-INDEPENDENT seed (and GradientReducer broadcasts rank 0's weights anyway)
 
     dim, size, patch, vocab = (128, 64, 16, 256) if args.small else (512, 256, 32, 65536)
+    vgg = None
+    if args.gan:
+        # .eval(): the reference's trainer leaves the VGG's Dropout(0.5) active (vae.train() reaches it); a fixed feature extractor is the evident intent
+        vgg = P.VGG16Features().load(args.vgg16).eval() if args.vgg16 else perceptual_stand_in(size)
     cvivit = P.CViViT(dim=dim, codebook_size=vocab, image_size=size, patch_size=patch, temporal_patch_size=2, spatial_depth=2 if args.small else 4,
                       temporal_depth=2 if args.small else 4, dim_head=64, heads=dim // 64, use_vgg_and_gan=args.gan,
-                      vgg=perceptual_stand_in(size) if args.gan else None).cuda().train()
+                      vgg=vgg).cuda().train()
+    if args.vgg16:
+        cvivit.vgg.eval()
     P.set_compute_dtype(cvivit, args.dtype)
     # the reference keeps two optimizers: the tokenizer's parameters (everything but discr.*) and the discriminator's (cvivit_trainer.py:118-124)
     params = [p for n, p in cvivit.named_parameters() if p.requires_grad and not n.startswith('discr.')]

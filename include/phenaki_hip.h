@@ -38,7 +38,7 @@ extern "C" {
 
 /* C = act(A @ W^T + bias) (+ res).  Replaces every nn.Linear on the path: attention.py:50-52 (FeedForward,
  * act 1 = GEGLU on interleaved (value, gate) column pairs -> C is [M][N/2]), attention.py:117-119 (to_q/to_kv/to_out),
- * attention.py:243-252 (CPB MLP, act 2 = LeakyReLU(0.1)), cvivit.py:276,283 (patch embed), cvivit.py:328,333
+ * attention.py:243-252 (CPB MLP, act 2 = LeakyReLU(0.1); act 3 = ReLU: the VGG16 classifier, cvivit.py:349-352), cvivit.py:276,283 (patch embed), cvivit.py:328,333
  * (to_pixels), phenaki_pytorch.py:147 (to_logits).
  * A [M][lda] is f32 (a_is_f32) or T; W [N][ldw] is T; bias [N] f32 or NULL; res [M][ldr] f32 or NULL;
  * C is f32 (out_is_f32) or T; a_rows (or NULL) gathers A rows: logical row m reads A[a_rows[m]]. */
@@ -548,6 +548,27 @@ int pk_row_l2scale(const float* x, const float* sc, const float* dz, const float
                    long long M, int d, int mode, void* stream);
 int pk_row_ln_bwd2(const float* x, const float* gamma, const float* dy, const float* u, const float* w, float eps, float* grad_x,
                    float* grad_gamma_rows, float* grad_dy, long long M, int D, void* stream);
+
+/* ---- the perceptual network of the tokenizer's GAN objective: reference cvivit.py:349-352 (torchvision VGG16, classifier[:-2]) and :636-651
+ * (F.mse_loss(vgg(frame), vgg(recon frame)), whose gradient reaches the tokenizer through the reconstructed frame).  Channels-last pixel rows
+ * x[(b, y, x)][c] as above, C % 8 == 0 (the 3-channel frame padded to 8 by pk_nchw_to_rows).  csrc/vgg.hip.
+ * pk_conv3x3: y[(b,y,x)][co] = act(bias[co] + sum_{ky,kx,c} x[(b, y+ky-1, x+kx-1)][c] W[co][(ky*3+kx)*C + c]), stride 1, pad 1, zero outside the image:
+ *   a DIRECT convolution (implicit GEMM, the patch matrix of pk_im2col is never written).  W [Co][ldw] is the pk_gemm weight image of `dtype` over
+ *   K = 9 C columns in pk_im2col's order (ldw >= K rounded up to 64 for dtype 1, 32 otherwise, zero padded: pk_pack); dtype / a_is_f32 / out_is_f32 as
+ *   pk_gemm (0 exact f32, 1 bf16 MFMA with f32 or bf16 x and y, 2 split-bf16 with W in the plane format).  act: 0 none, 1 ReLU; bias optional.
+ *   gate (optional; [B H W][ldg], f32 or bf16 by gate_is_f32): x[r][c] is read as 0 wherever gate[r][c] <= 0 -- with x = dy, gate = the saved post-ReLU
+ *   output and W = Wb, Wb[c][((2-ky)*3 + (2-kx))*Co + co] = W[co][(ky*3+kx)*C + c], this is the input gradient of relu(conv) (no weight gradient exists).
+ *   tile: 0 automatic, 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128 (rows x output channels per workgroup; tools/vgg_time.py).  Co % 4 == 0, B H W < 2^31 - 256.
+ * pk_maxpool2x2 / _bwd: nn.MaxPool2d(2, 2) on rows of f32 or bf16 (is_f32), output (H / 2) x (W / 2) (floor); the backward routes dy to the FIRST maximum
+ *   of each window in scan order (0,0), (0,1), (1,0), (1,1) (torch's rule), recomputed from the saved input x; gather form, deterministic; dy / dx f32.
+ * pk_adaptive_avgpool / _bwd: nn.AdaptiveAvgPool2d((7, 7)) with torch's windows [floor(i s / 7), ceil((i + 1) s / 7)), any H, W >= 1; out / dy
+ *   [(b, i, j)][c] f32; the backward in gather form. */
+int pk_conv3x3(int dtype, int a_is_f32, const void* x, int B, int H, int W, int C, const void* Wm, int ldw, int Co, const float* bias, int act,
+               const void* gate, int ldg, int gate_is_f32, void* y, int ldy, int out_is_f32, int tile, void* stream);
+int pk_maxpool2x2(int is_f32, const void* x, int B, int H, int W, int C, void* y, void* stream);
+int pk_maxpool2x2_bwd(int is_f32, const void* x, const float* dy, int B, int H, int W, int C, float* dx, void* stream);
+int pk_adaptive_avgpool(int is_f32, const void* x, int B, int H, int W, int C, float* out, void* stream);
+int pk_adaptive_avgpool_bwd(const float* dy, int B, int H, int W, int C, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

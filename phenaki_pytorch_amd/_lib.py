@@ -128,6 +128,11 @@ SIGNATURES = {
     'pk_row_softmax': [_P, _P, _P, _P, _LL, _I, _I, _P],
     'pk_row_l2scale': [_P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _P],
     'pk_row_ln_bwd2': [_P, _P, _P, _P, _P, _F, _P, _P, _P, _LL, _I, _P],
+    'pk_conv3x3': [_I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P],
+    'pk_maxpool2x2': [_I, _P, _I, _I, _I, _I, _P, _P],
+    'pk_maxpool2x2_bwd': [_I, _P, _P, _I, _I, _I, _I, _P, _P],
+    'pk_adaptive_avgpool': [_I, _P, _I, _I, _I, _I, _P, _P],
+    'pk_adaptive_avgpool_bwd': [_P, _I, _I, _I, _I, _P, _P],
 }
 
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
@@ -199,7 +204,7 @@ def require_device(t, name='tensor'):
 # compute dtypes of the C ABI: exact f32 MFMA | bf16 operands | split-bf16 ("bf16x3": every GEMM / attention product as
 # hi.hi + hi.lo + lo.hi on the bf16 matrix cores, operands x = bf16(x) + bf16(x - bf16(x)); activations stay f32 in memory)
 F32, BF16, BF16X3 = 0, 1, 2
-ACT_NONE, ACT_GEGLU, ACT_LEAKY = 0, 1, 2
+ACT_NONE, ACT_GEGLU, ACT_LEAKY, ACT_RELU = 0, 1, 2, 3
 
 
 def tdtype(dtype):
@@ -1034,6 +1039,54 @@ def row_ln_bwd2(x, gamma, dy, u, w, eps, grad_x, grad_gamma_rows, grad_dy):
     D = x.shape[-1]
     _check(load().pk_row_ln_bwd2(ptr(x), ptr(gamma), ptr(dy), ptr(u), ptr(w), float(eps), ptr(grad_x), ptr(grad_gamma_rows), ptr(grad_dy),
                                  x.numel() // D, D, stream(x)), 'pk_row_ln_bwd2')
+
+
+# ----------------------------------------------------------------------------- perceptual network kernels (csrc/vgg.hip)
+
+def _is_f32(t, what):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f'{what}: pixel rows are float32 or bfloat16, got {t.dtype}')
+    return 1 if t.dtype == torch.float32 else 0
+
+
+def conv3x3(dtype, x, W, B, H, Wd, C, Co, y, *, bias=None, relu=False, gate=None, tile=0):
+    """y (B H Wd, Co) = act(bias + the 3x3 / stride 1 / pad 1 convolution of the pixel rows x (B H Wd, C)); W (Co, Kpad): the pk_gemm weight image of
+    `dtype` over the 9 C columns in im2col order.  gate (B H Wd, C): x is read as 0 where gate <= 0 (the fused ReLU backward of the backward-data form)."""
+    for t, c, what in ((x, C, 'x'), (y, Co, 'y')) + (((gate, C, 'gate'),) if gate is not None else ()):
+        if not t.is_contiguous() or t.numel() != B * H * Wd * c:
+            raise RuntimeError(f'pk_conv3x3: {what} must be contiguous ({B * H * Wd}, {c}) pixel rows, got {tuple(t.shape)}')
+    rc = load().pk_conv3x3(dtype, _is_f32(x, 'x'), ptr(x), B, H, Wd, C, ptr(W), W.stride(0), Co, f32p(bias, 'bias'), 1 if relu else 0,
+                           ptr(gate), C if gate is not None else 0, _is_f32(gate, 'gate') if gate is not None else 1, ptr(y), Co, _is_f32(y, 'y'),
+                           int(tile), stream(x))
+    _check(rc, 'pk_conv3x3')
+    return y
+
+
+def maxpool2x2(x, B, H, Wd, C, y):
+    """nn.MaxPool2d(2, 2) on pixel rows: x (B H Wd, C) -> y (B (H // 2) (Wd // 2), C), same element type"""
+    assert x.dtype == y.dtype and x.is_contiguous() and y.is_contiguous() and x.numel() == B * H * Wd * C and y.numel() == B * (H // 2) * (Wd // 2) * C
+    _check(load().pk_maxpool2x2(_is_f32(x, 'x'), ptr(x), B, H, Wd, C, ptr(y), stream(x)), 'pk_maxpool2x2')
+    return y
+
+
+def maxpool2x2_bwd(x, dy, B, H, Wd, C, dx):
+    """dx (B H Wd, C) f32 <- dy (B (H // 2) (Wd // 2), C) f32 routed to the first maximum of every window of the saved input x"""
+    assert x.is_contiguous() and x.numel() == B * H * Wd * C and dx.numel() == x.numel() and dy.numel() == B * (H // 2) * (Wd // 2) * C
+    _check(load().pk_maxpool2x2_bwd(_is_f32(x, 'x'), ptr(x), f32p(dy, 'dy'), B, H, Wd, C, f32p(dx, 'dx'), stream(x)), 'pk_maxpool2x2_bwd')
+    return dx
+
+
+def adaptive_avgpool(x, B, H, Wd, C, out):
+    """nn.AdaptiveAvgPool2d((7, 7)) on pixel rows: x (B H Wd, C) f32 / bf16 -> out (B 49, C) f32, rows (b, i, j)"""
+    assert x.is_contiguous() and x.numel() == B * H * Wd * C and out.numel() == B * 49 * C
+    _check(load().pk_adaptive_avgpool(_is_f32(x, 'x'), ptr(x), B, H, Wd, C, f32p(out, 'out'), stream(x)), 'pk_adaptive_avgpool')
+    return out
+
+
+def adaptive_avgpool_bwd(dy, B, H, Wd, C, dx):
+    assert dy.numel() == B * 49 * C and dx.numel() == B * H * Wd * C
+    _check(load().pk_adaptive_avgpool_bwd(f32p(dy, 'dy'), B, H, Wd, C, f32p(dx, 'dx'), stream(dy)), 'pk_adaptive_avgpool_bwd')
+    return dx
 
 
 class TorchPhilox:

@@ -1,6 +1,6 @@
 // pk_gemm: every nn.Linear on the hot path (reference attention.py:50-52,117-119, cvivit.py:276,283,
 // 328,333, phenaki_pytorch.py:147) as one MFMA GEMM with a fused epilogue:
-//   C = act(A @ W^T + bias) (+ residual)        act in {none, GEGLU pair, LeakyReLU(0.1)}
+//   C = act(A @ W^T + bias) (+ residual)        act in {none, GEGLU pair, LeakyReLU(0.1), ReLU}
 // Roofline: MFMA-bound (bf16 2.5 PFLOP/s dense, exact-f32 157 TFLOP/s); algorithmic flops 2*M*N*K.
 // Two main loops share the epilogue: gemm_core.hpp (register-staged, converts f32 A on the fly) and
 // gemm_dma.hpp (LDS-DMA ring, A and W of the same type, W zero-padded along K to the k-tile).
@@ -9,7 +9,7 @@
 
 namespace pk {
 
-enum { ACT_NONE = 0, ACT_GEGLU = 1, ACT_LEAKY = 2 };
+enum { ACT_NONE = 0, ACT_GEGLU = 1, ACT_LEAKY = 2, ACT_RELU = 3 };
 
 struct GemmEpilogue {
     const float* bias;   // [N] or null
@@ -71,6 +71,7 @@ __device__ __forceinline__ void gemm_epilogue_scalar(const f32x4 (&acc)[TM][TN],
                     continue;
                 }
                 if (e.act == ACT_LEAKY) x = x > 0.f ? x : 0.1f * x;
+                if (e.act == ACT_RELU) x = fmaxf(x, 0.f);
                 if (e.res) x += e.res[(size_t)m * e.ldr + nn];
                 const size_t o = (size_t)m * e.ldc + nn;
                 if (e.out_f32) Cf[o] = x; else store_elem(Ct + o, x);
@@ -159,6 +160,10 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M,
                 if (e.act == ACT_LEAKY) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.1f * v[r];
+                }
+                if (e.act == ACT_RELU) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
                 }
                 if (!LNF) v += r4[ii][j];
                 else if (e.res && live) v += *reinterpret_cast<const f32x4*>(e.res + (size_t)m * e.ldr + n);
@@ -490,7 +495,7 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
                           const int* row_off, const int* col_off, float* stats_out, const float* ln_stats, int dup_rows, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C) return PK_EINVAL;
     if (dtype != 0 && dtype != 1 && dtype != 2) return PK_EINVAL;
-    if (act < 0 || act > 2) return PK_EINVAL;
+    if (act < 0 || act > 3) return PK_EINVAL;
     const int eps_w = dtype == 1 ? 8 : 4;                        // elements per 16 B of W (split-bf16: W is counted in 4-byte units, like f32)
     const int eps_a = (dtype == 1 && !a_is_f32) ? 8 : 4;         // alignment quantum of A rows
     if (K % eps_w || ldw % eps_w || lda % eps_a) return PK_EALIGN;
