@@ -10,6 +10,11 @@ DataLoader (data.py:177-265); without it synthetic videos stand in.  One process
     python examples/train_cvivit.py --steps 20 --small --gif /tmp/recon.gif
     python examples/train_cvivit.py --steps 20 --small --gan
     python examples/train_cvivit.py --steps 20 --gan --vgg16 vgg16.pt
+    python examples/train_cvivit.py --steps 20 --small --vq-kmeans-init --vq-dead-code 2
+
+`--vq-kmeans-init` / `--vq-dead-code T` train the Phenaki paper's cosine-sim VectorQuantize tokenizer (lookup_free_quantization=False) with the
+published module's codebook upkeep: k-means initialisation from the first batch, and replacement of codes whose EMA cluster size fell below T.
+Under torchrun the codebook statistics are computed from every rank's rows (sync_codebook), so all ranks keep one codebook.
 """
 import argparse
 import contextlib
@@ -51,6 +56,9 @@ def main():
     ap.add_argument('--vgg16', default='', metavar='PATH', help='with --gan: a torchvision vgg16 state dict (torch.save(vgg16.state_dict(), PATH)); the '
                     'perceptual network is then the real VGG16 (P.VGG16Features) instead of the stand-in')
     ap.add_argument('--gp-every', type=int, default=4, help='apply the gradient penalty every this many steps (cvivit_trainer.py:224)')
+    ap.add_argument('--vq-kmeans-init', action='store_true', help='the cosine-sim VectorQuantize tokenizer, its codebook initialised by k-means on the first batch')
+    ap.add_argument('--vq-dead-code', type=float, default=0., metavar='T', help='the cosine-sim VectorQuantize tokenizer with threshold_ema_dead_code = T: '
+                    'a code whose EMA cluster size falls below T is replaced by a row of the batch')
     args = ap.parse_args()
     ws = int(os.environ.get('WORLD_SIZE', '1'))
     if ws > 1:
@@ -61,12 +69,19 @@ def main():
 
     dim, size, patch, vocab = (128, 64, 16, 256) if args.small else (512, 256, 32, 65536)
     vgg = None
+    use_vq = args.vq_kmeans_init or args.vq_dead_code > 0
     if args.gan:
         # .eval(): the reference's trainer leaves the VGG's Dropout(0.5) active (vae.train() reaches it); a fixed feature extractor is the evident intent
         vgg = P.VGG16Features().load(args.vgg16).eval() if args.vgg16 else perceptual_stand_in(size)
     cvivit = P.CViViT(dim=dim, codebook_size=vocab, image_size=size, patch_size=patch, temporal_patch_size=2, spatial_depth=2 if args.small else 4,
                       temporal_depth=2 if args.small else 4, dim_head=64, heads=dim // 64, use_vgg_and_gan=args.gan,
-                      vgg=vgg).cuda().train()
+                      vgg=vgg, lookup_free_quantization=not use_vq)
+    if use_vq:
+        # the reference constructs the quantizer without keywords (cvivit.py:321): replace it (k-means starts from an empty codebook) and set the threshold
+        if args.vq_kmeans_init:
+            cvivit.vq = P.quantize.VectorQuantize(dim=dim, codebook_size=vocab, kmeans_init=True)
+        cvivit.vq.threshold_ema_dead_code = args.vq_dead_code
+    cvivit = cvivit.cuda().train()
     if args.vgg16:
         cvivit.vgg.eval()
     P.set_compute_dtype(cvivit, args.dtype)

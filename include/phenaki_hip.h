@@ -204,6 +204,29 @@ int pk_vq_gather_commit(const float* x, const float* E, const long long* ids, co
 int pk_vq_commit_bwd(const float* dy, const float* x, const float* q, const unsigned char* keep, int M, int D, float coef, const float* coef_dev,
                      float* dx, void* stream);
 
+/* Upkeep of the same codebook (the published module's threshold_ema_dead_code and kmeans_init; semantics restated in DESIGN.md "VectorQuantize
+ * upkeep", parity unpinned).  A row is chosen as pick(b, j, n) = ((b mod n) + j P) mod n, P = 2^31 - 1, in 64-bit integers, among the n kept rows
+ * in ascending order: kept / n_keep are the list and its length ON THE DEVICE (pk_vq_compact_keep), both NULL = every row kept (n = M).  b >= 0
+ * is a host integer.  Every index made from device data (jrank, n_keep, kept[]) is range-tested before use; a failed test leaves the EMA result.
+ *   pk_vq_compact_keep:           kept[0 .. n) = the rows with keep[r] != 0, ascending (M int32); n_keep[0] = n.  One workgroup.
+ *   pk_vq_scan_expire:            pk_vq_scan, and jrank[c] (V int32) = #{c' < c : cluster_size[c'] < threshold} where the post-EMA
+ *                                 cluster_size[c] < threshold (strict), -1 elsewhere.  S and cluster_size are exactly pk_vq_scan's.
+ *   pk_vq_codebook_update_expire: pk_vq_codebook_update, except that a code with jrank[c] = j >= 0 gets embed[c] = xn[r] (bit for bit),
+ *                                 embed_avg[c] = reset * xn[r], cluster_size[c] = reset, r = the j-th chosen row.
+ *   pk_vq_pick_rows:              out[c] = xn[the c-th chosen row], c < V (the k-means seeds; the published module samples them).
+ *   pk_vq_kmeans_means:           one k-means mean update after hist / scan / fill on the assignment: means[c] = l2norm(sum of xn over code c's
+ *                                 rows, ascending) where counts[c] > 0, untouched elsewhere.  embed_avg / cluster_size non-NULL (both or neither):
+ *                                 also embed_avg[c] = means[c] * counts[c], cluster_size[c] = counts[c] (the initialised state). */
+int pk_vq_compact_keep(const unsigned char* keep, int M, int* kept, int* n_keep, void* stream);
+int pk_vq_scan_expire(const int* counts, int V, float decay, float threshold, float* cluster_size, int* offsets, int* cursor, float* S, int* jrank,
+                      void* stream);
+int pk_vq_codebook_update_expire(const float* xn, const int* counts, const int* offsets, const int* rows, float* cluster_size, const float* S,
+                                 const int* jrank, const int* kept, const int* n_keep, int M, int V, int D, float decay, float eps, float reset,
+                                 long long b, float* embed_avg, float* embed, void* stream);
+int pk_vq_pick_rows(const float* xn, const int* kept, const int* n_keep, int M, int V, int D, long long b, float* out, void* stream);
+int pk_vq_kmeans_means(const float* xn, const int* counts, const int* offsets, const int* rows, int M, int V, int D, float* means, float* embed_avg,
+                       float* cluster_size, void* stream);
+
 /* Text-encoder support (reference t5.py:64-103 calls HuggingFace T5EncoderModel; the T5 v1.1 encoder layers are built
  * from pk_gemm, pk_attn_prep with q_scale = k_scale = NULL (plain dot-product attention: no l2norm, q * scale), pk_attn_fwd and these two):
  * pk_rmsnorm: T5LayerNorm, y = x * rsqrt(mean(x^2) + eps) * w (f32 statistics, no mean subtraction, no bias); rows with rowmask[row] == 0

@@ -56,6 +56,11 @@ SIGNATURES = {
     'pk_vq_codebook_update': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
     'pk_vq_gather_commit': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     'pk_vq_commit_bwd': [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P],
+    'pk_vq_compact_keep': [_P, _I, _P, _P, _P],
+    'pk_vq_scan_expire': [_P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
+    'pk_vq_codebook_update_expire': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _LL, _P, _P, _P],
+    'pk_vq_pick_rows': [_P, _P, _P, _I, _I, _I, _LL, _P, _P],
+    'pk_vq_kmeans_means': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     'pk_layernorm_lfq': [_P, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'pk_embed': [_P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P],
     'pk_cpb_input': [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -432,6 +437,77 @@ def vq_ema_update(xn, ids, keep, cluster_size, embed_avg, embed, decay, eps, che
     _check(lib.pk_vq_codebook_update(f32p(xn, 'xn'), ptr(counts), ptr(offsets), ptr(rows), cs, ptr(S), M, V, D, float(decay), float(eps), ea, em, st),
            'pk_vq_codebook_update')
     return counts
+
+
+def vq_compact_keep(keep):
+    """keep (M,) uint8 -> (kept (M,) int32: the kept row indices, ascending, in its first n entries; n_keep (1,) int32 = n), both on the device"""
+    M = keep.numel()
+    kept = torch.empty((M,), device=keep.device, dtype=torch.int32)
+    n_keep = torch.empty((1,), device=keep.device, dtype=torch.int32)
+    _check(load().pk_vq_compact_keep(ptr(keep), M, ptr(kept), ptr(n_keep), stream(keep)), 'pk_vq_compact_keep')
+    return kept, n_keep
+
+
+def vq_ema_update_expire(xn, ids, keep, cluster_size, embed_avg, embed, decay, eps, threshold, reset, b, check_ids=False):
+    """vq_ema_update followed by dead-code expiry in the same four launches (+ the compaction of `keep` when there is a mask): a code whose
+    post-EMA cluster_size is < threshold takes the j-th chosen kept row, j = its rank among the expired codes (pick(b, j, n_keep), host integer b):
+    embed = that row of xn, embed_avg = reset * it, cluster_size = reset.  Returns (counts, jrank) (V,) int32; jrank >= 0 marks the expired codes."""
+    lib = load()
+    M, D = xn.shape
+    V = embed.shape[0]
+    dev = xn.device
+    st = stream(xn)
+    counts = torch.zeros((V,), device=dev, dtype=torch.int32)
+    offsets, cursor, jrank = torch.empty_like(counts), torch.empty_like(counts), torch.empty_like(counts)
+    rows = torch.empty((M,), device=dev, dtype=torch.int32)
+    S = torch.empty((1,), device=dev, dtype=torch.float32)
+    if not (float(threshold) >= 0. and float(reset) >= 0. and int(b) >= 0):
+        _check(-1, 'vq_ema_update_expire (threshold, reset_cluster_size and b must be >= 0)')
+    kept, n_keep = vq_compact_keep(keep) if keep is not None else (None, None)
+    cs, ea, em = f32p(cluster_size, 'cluster_size'), f32p(embed_avg, 'embed_avg'), f32p(embed, 'embed')
+    _check(lib.pk_vq_hist(ptr(ids), ptr(keep), M, V, ptr(counts), 1 if check_ids else 0, st), 'pk_vq_hist')
+    _check(lib.pk_vq_scan_expire(ptr(counts), V, float(decay), float(threshold), cs, ptr(offsets), ptr(cursor), ptr(S), ptr(jrank), st), 'pk_vq_scan_expire')
+    _check(lib.pk_vq_fill(ptr(ids), ptr(keep), M, V, ptr(cursor), ptr(rows), st), 'pk_vq_fill')
+    _check(lib.pk_vq_codebook_update_expire(f32p(xn, 'xn'), ptr(counts), ptr(offsets), ptr(rows), cs, ptr(S), ptr(jrank), ptr(kept), ptr(n_keep), M, V, D,
+                                            float(decay), float(eps), float(reset), int(b), ea, em, st), 'pk_vq_codebook_update_expire')
+    return counts, jrank
+
+
+def vq_kmeans(data, keep, means, iters, b, lookup, *, embed_avg=None, cluster_size=None, trace=False):
+    """Spherical k-means on the kept rows of data (M, D) unit-norm f32, in place on means (V, D): seeds means[c] = the c-th chosen kept row
+    (pk_vq_pick_rows, host integer b), then `iters` times ids = lookup(data, means) (the exact-f32 cosine argmax, lower index on ties), counting
+    sort, means[c] = l2norm(sum of its rows, ascending) where a code has rows.  embed_avg (V, D) / cluster_size (V,): written by the LAST
+    iteration as means * bins and bins.  Returns (means, bins (V,) int32 of the last assignment, ids (iters, M) int64[, the means after every
+    iteration (iters, V, D) with trace])."""
+    lib = load()
+    M, D = data.shape
+    V = means.shape[0]
+    dev = data.device
+    st = stream(data)
+    if int(iters) < 1:
+        _check(-1, 'vq_kmeans (kmeans_iters < 1)')
+    kept, n_keep = vq_compact_keep(keep) if keep is not None else (None, None)
+    mp = f32p(means, 'means')
+    _check(lib.pk_vq_pick_rows(f32p(data, 'data'), ptr(kept), ptr(n_keep), M, V, D, int(b), mp, st), 'pk_vq_pick_rows')
+    offsets, cursor = (torch.empty((V,), device=dev, dtype=torch.int32) for _ in range(2))
+    rows = torch.empty((M,), device=dev, dtype=torch.int32)
+    S, scratch = torch.empty((1,), device=dev, dtype=torch.float32), torch.empty((V,), device=dev, dtype=torch.float32)
+    all_ids, all_means, counts = [], [], None
+    for it in range(int(iters)):
+        ids = lookup(data, means)
+        counts = torch.zeros((V,), device=dev, dtype=torch.int32)
+        scratch.zero_()                                               # the scan's EMA of cluster_size lands here, never in the module's buffer
+        last = it == int(iters) - 1 and embed_avg is not None
+        _check(lib.pk_vq_hist(ptr(ids), ptr(keep), M, V, ptr(counts), 0, st), 'pk_vq_hist')
+        _check(lib.pk_vq_scan(ptr(counts), V, 1.0, ptr(scratch), ptr(offsets), ptr(cursor), ptr(S), st), 'pk_vq_scan')
+        _check(lib.pk_vq_fill(ptr(ids), ptr(keep), M, V, ptr(cursor), ptr(rows), st), 'pk_vq_fill')
+        _check(lib.pk_vq_kmeans_means(f32p(data, 'data'), ptr(counts), ptr(offsets), ptr(rows), M, V, D, mp, f32p(embed_avg, 'embed_avg') if last else None,
+                                      f32p(cluster_size, 'cluster_size') if last else None, st), 'pk_vq_kmeans_means')
+        all_ids.append(ids)
+        if trace:
+            all_means.append(means.clone())
+    out = (means, counts, torch.stack(all_ids))
+    return out + (torch.stack(all_means),) if trace else out
 
 
 def embed(ids, tok, pos, out, S, n, D, *, nb=None, ids_prime=None, out_t=None):

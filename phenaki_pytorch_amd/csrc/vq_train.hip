@@ -16,6 +16,17 @@
 //     pk_vq_fill             one thread per kept row: rows[atomicAdd(cursor[id], 1)] = r
 //     pk_vq_codebook_update  one wave per code, four codes per workgroup, grid-stride: a pure stream over embed_avg (read + write) and embed (write)
 //
+// Upkeep of the codebook (DESIGN.md "VectorQuantize upkeep"; the published module's threshold_ema_dead_code and kmeans_init, restated there):
+//
+//     pick(b, j, n) = ((b mod n) + j P) mod n,  P = 2^31 - 1 (prime: a bijection of [0, n) in j for n < P), 64-bit integers; the j-th choice is the
+//     pick-th KEPT row (pk_vq_compact_keep lists them in ascending order; no mask: the identity).  b is a host integer.
+//
+//     dead-code expiry   pk_vq_scan_expire is pk_vq_scan that also ranks the codes whose post-EMA size is < threshold (jrank[c] = j(c), -1 otherwise);
+//                        pk_vq_codebook_update_expire is pk_vq_codebook_update whose wave, for a ranked code, writes embed[c] = xn[r(c)],
+//                        embed_avg[c] = reset xn[r(c)], cluster_size[c] = reset instead of the EMA result: no extra launch, no second stream.
+//     k-means init       pk_vq_pick_rows seeds means[c] = data[pick(b, c, n)]; an iteration is the lookup, hist / scan (on a scratch cluster_size) /
+//                        fill, and pk_vq_kmeans_means: the same ascending-row segment sum, means[c] = l2norm(sum[c]) where bins[c] > 0.
+//
 // ids are device data: every kernel that indexes with one tests 0 <= id < V first and treats the row as dropped otherwise, so a bad id can never turn
 // into an address.  pk_vq_hist(check_ids = 1) additionally copies the ids to the host (one stream synchronisation) and refuses them with PK_EINVAL
 // before anything is launched; the training step passes 0 (its ids come out of the library's own argmax kernel).
@@ -52,16 +63,20 @@ __global__ __launch_bounds__(256) void vq_hist_kernel(const long long* __restric
 // One workgroup of 16 waves; wave w owns `tiles` consecutive tiles of 64 codes, one code per lane, so every access is a coalesced 256-byte row and the
 // loads of a batch of four tiles are in flight together.  Pass 1: EMA of cluster_size, the wave's count total and its share of S.  Pass 2: exclusive
 // scan, a shuffle scan per tile on top of a running base.  S is summed lane-serially, then by the butterfly, then over the waves in order: one fixed order.
+// EXPIRE: the flags (post-EMA size < threshold, strict) are scanned beside the counts: jrank[c] = the number of flagged codes below c, -1 for the others.
+template <bool EXPIRE>
 __global__ __launch_bounds__(VQ_SCAN_THREADS) void vq_scan_kernel(const int* __restrict__ counts, int V, float decay, float* __restrict__ cluster_size,
-                                                                  int* __restrict__ offsets, int* __restrict__ cursor, float* __restrict__ S) {
+                                                                  int* __restrict__ offsets, int* __restrict__ cursor, float* __restrict__ S,
+                                                                  float threshold, int* __restrict__ jrank) {
     constexpr int WAVES = VQ_SCAN_THREADS / 64;
     __shared__ int wtot[WAVES];
+    __shared__ int wexp[WAVES];
     __shared__ float wsum[WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tiles = ((V + WAVES - 1) / WAVES + 63) / 64;
     const int base = wave * tiles * 64 + lane;
     const float grow = 1.0f - decay;
-    int n = 0;
+    int n = 0, nx = 0;
     float s = 0.f;
     for (int i0 = 0; i0 < tiles; i0 += 4) {
         int k[4];
@@ -81,16 +96,24 @@ __global__ __launch_bounds__(VQ_SCAN_THREADS) void vq_scan_kernel(const int* __r
                 cluster_size[c] = v;
                 n += k[u];
                 s += v;
+                if (EXPIRE) nx += v < threshold ? 1 : 0;
             }
         }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
     s = wave_sum(s);
+    if (EXPIRE) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nx += __shfl_xor(nx, o, 64);
+    }
     if (lane == 0) { wtot[wave] = n; wsum[wave] = s; }
+    if (EXPIRE && lane == 0) wexp[wave] = nx;
     __syncthreads();
-    int run = 0;
+    int run = 0, runx = 0;
     for (int w = 0; w < wave; ++w) run += wtot[w];
+    if (EXPIRE)
+        for (int w = 0; w < wave; ++w) runx += wexp[w];
     for (int i0 = 0; i0 < tiles; i0 += 4) {
         int k[4];
 #pragma unroll
@@ -112,6 +135,18 @@ __global__ __launch_bounds__(VQ_SCAN_THREADS) void vq_scan_kernel(const int* __r
                 cursor[c] = run + inc - k[u];
             }
             run += __shfl(inc, 63, 64);
+            if (EXPIRE) {
+                // (this thread's own pass-1 store: the same thread owns code c in both passes)
+                const int dead = (i0 + u < tiles && c < V && cluster_size[c] < threshold) ? 1 : 0;
+                int incx = dead;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int y = __shfl_up(incx, o, 64);
+                    if (lane >= o) incx += y;
+                }
+                if (i0 + u < tiles && c < V) jrank[c] = dead ? runx + incx - 1 : -1;
+                runx += __shfl(incx, 63, 64);
+            }
         }
     }
     if (threadIdx.x == 0) {
@@ -131,50 +166,86 @@ __global__ __launch_bounds__(256) void vq_fill_kernel(const long long* __restric
     if ((unsigned)pos < (unsigned)M) rows[pos] = r;
 }
 
-// One wave per code.  The code's segment of `rows` is walked in ascending row index by repeated minimum extraction: a segment of <= 64 rows (all
-// but a collapsed codebook's) sits one row per lane in a register and each step is six shuffles; a longer one is re-read per step (n^2 / 64 loads).
+// The segment walk one wave does for its code: the code's segment of `rows` in ascending row index by repeated minimum extraction.  A segment of
+// <= 64 rows (all but a collapsed codebook's) sits one row per lane in a register and each step is six shuffles; a longer one is re-read per step
+// (n^2 / 64 loads).  acc = sum of xn[r] over the segment, lane-strided 16-byte chunks.
+__device__ __forceinline__ void vq_segment_sum(const float* __restrict__ xn, const int* __restrict__ counts, const int* __restrict__ offsets,
+                                               const int* __restrict__ rows, int c, int M, int D, int lane, f32x4 (&acc)[VQ_KMAX]) {
+    const int nq = D >> 2;
+    int n = counts[c];
+    const int off = offsets[c];
+    if (n < 0 || off < 0 || off > M - n) n = 0;                      // (never taken after pk_vq_hist / scan / fill on the same ids)
+#pragma unroll
+    for (int k = 0; k < VQ_KMAX; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int mine = (n <= 64 && lane < n) ? rows[off + lane] : INT_MAX;
+    int last = -1;
+    for (int j = 0; j < n; ++j) {
+        int cand = INT_MAX;
+        if (n <= 64) {
+            cand = mine > last ? mine : INT_MAX;
+        } else {
+            for (int i = lane; i < n; i += 64) {
+                const int v = rows[off + i];
+                if (v > last && v < cand) cand = v;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+        if ((unsigned)cand >= (unsigned)M) break;
+        const f32x4* row = reinterpret_cast<const f32x4*>(xn + (size_t)cand * D);
+#pragma unroll
+        for (int k = 0; k < VQ_KMAX; ++k) {
+            const int q = lane + 64 * k;
+            if (q < nq) acc[k] += row[q];
+        }
+        last = cand;
+    }
+}
+
+constexpr long long VQ_PICK_P = 2147483647LL;                       // 2^31 - 1
+
+// The j-th chosen row, or -1: pick(b, j, n) = ((b mod n) + j P) mod n over the n kept rows (kept NULL: the identity, n = M; else n = n_keep[0] and
+// the row is kept[pick]).  n, the position and the row read from `kept` are device data and are range-tested before they are used.
+__device__ __forceinline__ int vq_pick_row(long long b, int j, const int* __restrict__ kept, const int* __restrict__ n_keep, int M) {
+    const int n = kept ? n_keep[0] : M;
+    if (n <= 0 || n > M || j < 0 || b < 0) return -1;
+    const long long p = ((b % n) + (long long)j * VQ_PICK_P) % n;
+    const int r = kept ? kept[p] : (int)p;
+    return (unsigned)r < (unsigned)M ? r : -1;
+}
+
+// One wave per code.  EXPIRE: a code ranked by pk_vq_scan_expire (jrank[c] >= 0) takes the chosen row instead of the EMA result.
+template <bool EXPIRE>
 __global__ __launch_bounds__(256) void vq_codebook_update_kernel(const float* __restrict__ xn, const int* __restrict__ counts, const int* __restrict__ offsets,
-                                                                 const int* __restrict__ rows, const float* __restrict__ cluster_size,
-                                                                 const float* __restrict__ S, int M, int V, int D, float decay, float eps,
-                                                                 float* __restrict__ embed_avg, float* __restrict__ embed) {
+                                                                 const int* __restrict__ rows, float* __restrict__ cluster_size,
+                                                                 const float* __restrict__ S, const int* __restrict__ jrank, const int* __restrict__ kept,
+                                                                 const int* __restrict__ n_keep, int M, int V, int D, float decay, float eps, float reset,
+                                                                 long long b, float* __restrict__ embed_avg, float* __restrict__ embed) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nq = D >> 2;
     const float Sv = S[0];
     const float denom = Sv + (float)V * eps;
     const float grow = 1.0f - decay;
     for (int c = blockIdx.x * 4 + wave; c < V; c += gridDim.x * 4) {
-        int n = counts[c];
-        const int off = offsets[c];
-        if (n < 0 || off < 0 || off > M - n) n = 0;                      // (never taken after pk_vq_hist / scan / fill on the same ids)
-        f32x4 acc[VQ_KMAX];
-#pragma unroll
-        for (int k = 0; k < VQ_KMAX; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int mine = (n <= 64 && lane < n) ? rows[off + lane] : INT_MAX;
-        int last = -1;
-        for (int j = 0; j < n; ++j) {
-            int cand = INT_MAX;
-            if (n <= 64) {
-                cand = mine > last ? mine : INT_MAX;
-            } else {
-                for (int i = lane; i < n; i += 64) {
-                    const int v = rows[off + i];
-                    if (v > last && v < cand) cand = v;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-            if ((unsigned)cand >= (unsigned)M) break;
-            const f32x4* row = reinterpret_cast<const f32x4*>(xn + (size_t)cand * D);
-#pragma unroll
-            for (int k = 0; k < VQ_KMAX; ++k) {
-                const int q = lane + 64 * k;
-                if (q < nq) acc[k] += row[q];
-            }
-            last = cand;
-        }
-        const float smoothed = (cluster_size[c] + eps) / denom * Sv;
         f32x4* avg = reinterpret_cast<f32x4*>(embed_avg + (size_t)c * D);
         f32x4* out = reinterpret_cast<f32x4*>(embed + (size_t)c * D);
+        if (EXPIRE) {
+            const int j = jrank[c];
+            const int r = j >= 0 ? vq_pick_row(b, j, kept, n_keep, M) : -1;
+            if (r >= 0) {                                                // (wave-uniform: c, j and r are)
+                const f32x4* row = reinterpret_cast<const f32x4*>(xn + (size_t)r * D);
+                for (int q = lane; q < nq; q += 64) {
+                    const f32x4 v = row[q];
+                    out[q] = v;
+                    avg[q] = v * reset;
+                }
+                if (lane == 0) cluster_size[c] = reset;
+                continue;
+            }
+        }
+        f32x4 acc[VQ_KMAX];
+        vq_segment_sum(xn, counts, offsets, rows, c, M, D, lane, acc);
+        const float smoothed = (cluster_size[c] + eps) / denom * Sv;
         f32x4 e[VQ_KMAX];
         float sq = 0.f;
 #pragma unroll
@@ -194,6 +265,88 @@ __global__ __launch_bounds__(256) void vq_codebook_update_kernel(const float* __
             if (q < nq) out[q] = e[k] * inv;
         }
     }
+}
+
+// k-means: one wave per code, the same segment sum; means[c] = l2norm(sum[c]) where the code has rows, left alone where it has none.  With
+// embed_avg / cluster_size (the last iteration) the initialised state is written beside it: embed_avg[c] = means[c] * bins[c], cluster_size[c] = bins[c].
+__global__ __launch_bounds__(256) void vq_kmeans_means_kernel(const float* __restrict__ xn, const int* __restrict__ counts, const int* __restrict__ offsets,
+                                                              const int* __restrict__ rows, int M, int V, int D, float* __restrict__ means,
+                                                              float* __restrict__ embed_avg, float* __restrict__ cluster_size) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nq = D >> 2;
+    for (int c = blockIdx.x * 4 + wave; c < V; c += gridDim.x * 4) {
+        f32x4 acc[VQ_KMAX];
+        vq_segment_sum(xn, counts, offsets, rows, c, M, D, lane, acc);
+        int n = counts[c];
+        if (n < 0 || n > M) n = 0;
+        f32x4* mean = reinterpret_cast<f32x4*>(means + (size_t)c * D);
+        if (n > 0) {
+            float sq = 0.f;
+#pragma unroll
+            for (int k = 0; k < VQ_KMAX; ++k)
+                if (lane + 64 * k < nq) sq += acc[k].x * acc[k].x + acc[k].y * acc[k].y + acc[k].z * acc[k].z + acc[k].w * acc[k].w;
+            const float inv = 1.0f / fmaxf(sqrtf(wave_sum(sq)), 1e-12f);
+#pragma unroll
+            for (int k = 0; k < VQ_KMAX; ++k) {
+                const int q = lane + 64 * k;
+                if (q < nq) {
+                    acc[k] = acc[k] * inv;
+                    mean[q] = acc[k];
+                }
+            }
+        } else if (embed_avg) {
+#pragma unroll
+            for (int k = 0; k < VQ_KMAX; ++k) {
+                const int q = lane + 64 * k;
+                if (q < nq) acc[k] = mean[q];
+            }
+        }
+        if (embed_avg) {
+            f32x4* avg = reinterpret_cast<f32x4*>(embed_avg + (size_t)c * D);
+#pragma unroll
+            for (int k = 0; k < VQ_KMAX; ++k) {
+                const int q = lane + 64 * k;
+                if (q < nq) avg[q] = acc[k] * (float)n;
+            }
+            if (lane == 0) cluster_size[c] = (float)n;
+        }
+    }
+}
+
+// out[c] = xn[the c-th chosen row] (the k-means seeds); a choice that fails its range test leaves zeros
+__global__ __launch_bounds__(256) void vq_pick_rows_kernel(const float* __restrict__ xn, const int* __restrict__ kept, const int* __restrict__ n_keep, int M,
+                                                           int V, int D, long long b, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= V) return;
+    const int r = vq_pick_row(b, c, kept, n_keep, M);
+    const f32x4* row = reinterpret_cast<const f32x4*>(xn + (size_t)(r >= 0 ? r : 0) * D);
+    f32x4* o = reinterpret_cast<f32x4*>(out + (size_t)c * D);
+    for (int q = lane; q < (D >> 2); q += 64) o[q] = r >= 0 ? row[q] : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// One workgroup: kept[0 .. n) = the indices of the rows `keep` keeps, ascending; n_keep[0] = n.  Thread t owns a run of consecutive rows.
+__global__ __launch_bounds__(VQ_SCAN_THREADS) void vq_compact_keep_kernel(const unsigned char* __restrict__ keep, int M, int* __restrict__ kept,
+                                                                          int* __restrict__ n_keep) {
+    constexpr int WAVES = VQ_SCAN_THREADS / 64;
+    __shared__ int wtot[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int per = (M + VQ_SCAN_THREADS - 1) / VQ_SCAN_THREADS;
+    const int lo = min(M, (int)threadIdx.x * per), hi = min(M, lo + per);
+    int n = 0;
+    for (int r = lo; r < hi; ++r) n += keep[r] ? 1 : 0;
+    int inc = n;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    if (lane == 63) wtot[wave] = inc;
+    __syncthreads();
+    int pos = inc - n;
+    for (int w = 0; w < wave; ++w) pos += wtot[w];
+    for (int r = lo; r < hi; ++r)
+        if (keep[r] && (unsigned)pos < (unsigned)M) kept[pos++] = r;
+    if (threadIdx.x == VQ_SCAN_THREADS - 1) n_keep[0] = pos;
 }
 
 // one wave per row: y[r] = E[ids[r]], rowsq[r] = sum_d (E[ids[r]][d] - x[r][d])^2 for kept rows, 0 for dropped ones
@@ -261,7 +414,27 @@ extern "C" int pk_vq_hist(const long long* ids, const unsigned char* keep, int M
 extern "C" int pk_vq_scan(const int* counts, int V, float decay, float* cluster_size, int* offsets, int* cursor, float* S, void* stream) {
     if (!counts || !cluster_size || !offsets || !cursor || !S || V <= 0 || !(decay >= 0.f && decay <= 1.f)) return PK_EINVAL;
     if (mis4(counts) || mis4(cluster_size) || mis4(offsets) || mis4(cursor) || mis4(S)) return PK_EALIGN;
-    hipLaunchKernelGGL(vq_scan_kernel, dim3(1), dim3(VQ_SCAN_THREADS), 0, STREAM(stream), counts, V, decay, cluster_size, offsets, cursor, S);
+    hipLaunchKernelGGL(vq_scan_kernel<false>, dim3(1), dim3(VQ_SCAN_THREADS), 0, STREAM(stream), counts, V, decay, cluster_size, offsets, cursor, S, 0.f,
+                       (int*)nullptr);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_vq_scan_expire(const int* counts, int V, float decay, float threshold, float* cluster_size, int* offsets, int* cursor, float* S,
+                                 int* jrank, void* stream) {
+    if (!counts || !cluster_size || !offsets || !cursor || !S || !jrank || V <= 0 || !(decay >= 0.f && decay <= 1.f) || !(threshold >= 0.f))
+        return PK_EINVAL;
+    if (mis4(counts) || mis4(cluster_size) || mis4(offsets) || mis4(cursor) || mis4(S) || mis4(jrank)) return PK_EALIGN;
+    hipLaunchKernelGGL(vq_scan_kernel<true>, dim3(1), dim3(VQ_SCAN_THREADS), 0, STREAM(stream), counts, V, decay, cluster_size, offsets, cursor, S, threshold,
+                       jrank);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_vq_compact_keep(const unsigned char* keep, int M, int* kept, int* n_keep, void* stream) {
+    if (!keep || !kept || !n_keep || M <= 0) return PK_EINVAL;
+    if (mis4(kept) || mis4(n_keep)) return PK_EALIGN;
+    hipLaunchKernelGGL(vq_compact_keep_kernel, dim3(1), dim3(VQ_SCAN_THREADS), 0, STREAM(stream), keep, M, kept, n_keep);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
@@ -281,8 +454,45 @@ extern "C" int pk_vq_codebook_update(const float* xn, const int* counts, const i
         return PK_EINVAL;
     if (mis16(xn) || mis16(embed_avg) || mis16(embed) || mis4(counts) || mis4(offsets) || mis4(rows) || mis4(cluster_size) || mis4(S)) return PK_EALIGN;
     const int blocks = (V + 3) / 4 < 2048 ? (V + 3) / 4 : 2048;                        // 8 workgroups of 4 waves on each of the 256 CUs, grid-stride over the codes
-    hipLaunchKernelGGL(vq_codebook_update_kernel, dim3(blocks), dim3(256), 0, STREAM(stream), xn, counts, offsets, rows, cluster_size, S, M, V, D, decay, eps,
+    hipLaunchKernelGGL(vq_codebook_update_kernel<false>, dim3(blocks), dim3(256), 0, STREAM(stream), xn, counts, offsets, rows,
+                       const_cast<float*>(cluster_size), S, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, M, V, D, decay, eps, 0.f, 0LL,
                        embed_avg, embed);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_vq_codebook_update_expire(const float* xn, const int* counts, const int* offsets, const int* rows, float* cluster_size, const float* S,
+                                            const int* jrank, const int* kept, const int* n_keep, int M, int V, int D, float decay, float eps,
+                                            float reset, long long b, float* embed_avg, float* embed, void* stream) {
+    if (!xn || !counts || !offsets || !rows || !cluster_size || !S || !jrank || !embed_avg || !embed || (kept != nullptr) != (n_keep != nullptr) ||
+        bad_rows(M, V) || bad_width(D) || !(decay >= 0.f && decay <= 1.f) || !(eps > 0.f) || !(reset >= 0.f) || b < 0)
+        return PK_EINVAL;
+    if (mis16(xn) || mis16(embed_avg) || mis16(embed) || mis4(counts) || mis4(offsets) || mis4(rows) || mis4(cluster_size) || mis4(S) || mis4(jrank) ||
+        (kept && (mis4(kept) || mis4(n_keep))))
+        return PK_EALIGN;
+    const int blocks = (V + 3) / 4 < 2048 ? (V + 3) / 4 : 2048;
+    hipLaunchKernelGGL(vq_codebook_update_kernel<true>, dim3(blocks), dim3(256), 0, STREAM(stream), xn, counts, offsets, rows, cluster_size, S, jrank, kept,
+                       n_keep, M, V, D, decay, eps, reset, b, embed_avg, embed);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_vq_pick_rows(const float* xn, const int* kept, const int* n_keep, int M, int V, int D, long long b, float* out, void* stream) {
+    if (!xn || !out || (kept != nullptr) != (n_keep != nullptr) || bad_rows(M, V) || bad_width(D) || b < 0) return PK_EINVAL;
+    if (mis16(xn) || mis16(out) || (kept && (mis4(kept) || mis4(n_keep)))) return PK_EALIGN;
+    hipLaunchKernelGGL(vq_pick_rows_kernel, dim3((V + 3) / 4), dim3(256), 0, STREAM(stream), xn, kept, n_keep, M, V, D, b, out);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_vq_kmeans_means(const float* xn, const int* counts, const int* offsets, const int* rows, int M, int V, int D, float* means,
+                                  float* embed_avg, float* cluster_size, void* stream) {
+    if (!xn || !counts || !offsets || !rows || !means || (embed_avg != nullptr) != (cluster_size != nullptr) || bad_rows(M, V) || bad_width(D))
+        return PK_EINVAL;
+    if (mis16(xn) || mis16(means) || mis4(counts) || mis4(offsets) || mis4(rows) || (embed_avg && (mis16(embed_avg) || mis4(cluster_size))))
+        return PK_EALIGN;
+    const int blocks = (V + 3) / 4 < 2048 ? (V + 3) / 4 : 2048;
+    hipLaunchKernelGGL(vq_kmeans_means_kernel, dim3(blocks), dim3(256), 0, STREAM(stream), xn, counts, offsets, rows, M, V, D, means, embed_avg, cluster_size);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

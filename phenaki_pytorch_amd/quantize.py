@@ -100,13 +100,44 @@ class LFQ(nn.Module):
         return q.reshape(b, n, d), ids.reshape(b, n), torch.zeros((), device=x.device)
 
 
-class _CosineSimCodebook(nn.Module):
-    """holder mirroring the library's `_codebook` sub-module: `embed` is (1, codebook_size, dim), unit-norm rows."""
+PICK_P = 2 ** 31 - 1                     # prime: j -> (b + j P) mod n is a bijection of [0, n) for every n < P
+UPKEEP_EXPIRE, UPKEEP_KMEANS = 1, 2      # the `purpose` word of upkeep_mix
+_M64 = (1 << 64) - 1
 
-    def __init__(self, dim, codebook_size):
+
+def pick(b, j, n):
+    """position of the j-th chosen row among n kept rows (the kernels' vq_pick_row: the same 64-bit integer arithmetic): distinct while
+    j < n (the published randperm branch), wrapping evenly beyond (its randint branch)"""
+    return ((b % n) + j * PICK_P) % n
+
+
+def _splitmix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def upkeep_mix(seed, call, purpose):
+    """the host integer b of one upkeep draw: three chained splitmix64 finalisers over (upkeep_seed, call index, purpose), top 62 bits.  Ranks
+    running the same script draw the same b without talking to each other."""
+    z = _splitmix64(int(seed) & _M64)
+    z = _splitmix64(z ^ (int(call) & _M64))
+    z = _splitmix64(z ^ (int(purpose) & _M64))
+    return z >> 2
+
+
+class _CosineSimCodebook(nn.Module):
+    """holder mirroring the library's `_codebook` sub-module: `embed` is (1, codebook_size, dim), unit-norm rows -- or, with kmeans_init, zeros
+    and initted = False until the first training-mode call has run k-means on its rows (as published)."""
+
+    def __init__(self, dim, codebook_size, kmeans_init=False):
         super().__init__()
-        embed = torch.nn.functional.normalize(torch.randn(1, codebook_size, dim), dim=-1)
-        self.register_buffer('initted', torch.tensor([True]))
+        if kmeans_init:
+            embed = torch.zeros(1, codebook_size, dim)
+        else:
+            embed = torch.nn.functional.normalize(torch.randn(1, codebook_size, dim), dim=-1)
+        self.register_buffer('initted', torch.tensor([not kmeans_init]))
         self.register_buffer('cluster_size', torch.zeros(1, codebook_size))
         self.register_buffer('embed_avg', embed.clone())
         self.register_buffer('embed', embed)
@@ -124,16 +155,71 @@ class VectorQuantize(nn.Module):
     Training mode (`self.training`, the predicate of LFQ.forward): the straight-through output, the commitment loss
     commitment_weight * mean (q - x)^2 and the EMA update (decay, eps) of the `_codebook` buffers cluster_size /
     embed_avg / embed from the rows `mask` keeps -- train_cvivit._VQFn on the pk_vq_* kernels.  One head, no
-    projections, no k-means initialisation, no dead-code expiry, statistics per rank."""
+    projections (INTEGRATION.md).
 
-    def __init__(self, *, dim, codebook_size, use_cosine_sim=True, decay=0.8, eps=1e-5, commitment_weight=1.0, **_unused):
+    Upkeep (DESIGN.md "VectorQuantize upkeep"; every keyword is an attribute and may be set after construction, the defaults are off):
+      threshold_ema_dead_code = T > 0: after the EMA update a code whose cluster_size fell below T is replaced by a kept row of the batch
+        (cluster_size := reset_cluster_size, None = T), inside the update's own launches;
+      kmeans_init: the codebook starts at zeros with initted = False, and the first training-mode call runs kmeans_iters rounds of spherical
+        k-means on its kept rows before the ordinary step;
+      sync_codebook: None = when a process group of more than one rank is initialised, the statistics are computed from every rank's rows
+        (xn, ids and keep are all-gathered in rank order and each rank runs the same deterministic kernels: bit-identical buffers, no
+        broadcast); every rank must pass the same number of rows.  False = per rank (warns once), True without a process group = ValueError.
+      The rows upkeep draws are pick(b, j, n) with b = upkeep_mix(upkeep_seed, call index, purpose); `last_upkeep` records the b of the
+      latest training-mode call.  The call index is a plain counter (not in the state_dict)."""
+
+    def __init__(self, *, dim, codebook_size, use_cosine_sim=True, decay=0.8, eps=1e-5, commitment_weight=1.0, kmeans_init=False, kmeans_iters=10,
+                 threshold_ema_dead_code=0, reset_cluster_size=None, sync_codebook=None, upkeep_seed=0, **_unused):
         super().__init__()
         assert use_cosine_sim, 'only the cosine-sim codebook (the reference construction, cvivit.py:321) is built'
         assert dim % 32 == 0 and codebook_size % 4 == 0
         assert 0. <= decay <= 1. and eps > 0.
         self.dim, self.codebook_size = dim, codebook_size
         self.decay, self.eps, self.commitment_weight = float(decay), float(eps), float(commitment_weight)
-        self._codebook = _CosineSimCodebook(dim, codebook_size)
+        self.kmeans_init, self.kmeans_iters = bool(kmeans_init), int(kmeans_iters)
+        self.threshold_ema_dead_code, self.reset_cluster_size = threshold_ema_dead_code, reset_cluster_size
+        self.sync_codebook, self.upkeep_seed = sync_codebook, int(upkeep_seed)
+        self.upkeep_calls = 0
+        self.last_upkeep = None
+        self._initted_host = None                                   # the host's copy of `initted`, read from the buffer once
+        self._codebook = _CosineSimCodebook(dim, codebook_size, self.kmeans_init)
+        self.register_load_state_dict_post_hook(lambda module, _keys: setattr(module, '_initted_host', None))
+
+    def sync_world(self):
+        """the number of ranks whose rows enter the codebook statistics (1: this rank's alone)"""
+        import torch.distributed as dist
+        up = dist.is_available() and dist.is_initialized()
+        if self.sync_codebook is None:
+            return dist.get_world_size() if up else 1
+        if not self.sync_codebook:
+            return 1
+        if not up:
+            raise ValueError('VectorQuantize(sync_codebook=True) needs an initialised process group')
+        return dist.get_world_size()
+
+    def needs_kmeans(self):
+        """True until the codebook is initialised (kmeans_init only).  `initted` is read from the device once and remembered on the host."""
+        if not self.kmeans_init:
+            return False
+        if self._initted_host is None:
+            self._initted_host = bool(self._codebook.initted.item())
+        return not self._initted_host
+
+    def begin_upkeep(self):
+        """the draws of one training-mode call: dict(call, kmeans_b, expire_b) (None where that upkeep does not run); advances the call index"""
+        threshold = float(self.threshold_ema_dead_code)
+        if not threshold >= 0. or (self.kmeans_init and self.kmeans_iters < 1):
+            raise ValueError('VectorQuantize: threshold_ema_dead_code must be >= 0 and kmeans_iters >= 1')
+        call = self.upkeep_calls
+        self.upkeep_calls += 1
+        self.last_upkeep = dict(call=call,
+                                kmeans_b=upkeep_mix(self.upkeep_seed, call, UPKEEP_KMEANS) if self.needs_kmeans() else None,
+                                expire_b=upkeep_mix(self.upkeep_seed, call, UPKEEP_EXPIRE) if threshold > 0. else None)
+        return self.last_upkeep
+
+    def kmeans_done(self):
+        self._codebook.initted.fill_(True)
+        self._initted_host = True
 
     @property
     def codebook(self):
@@ -147,10 +233,11 @@ class VectorQuantize(nn.Module):
         L.l2norm_rows(x2d, xn, M, D)
         return xn
 
-    def ids_of_normalised(self, xn):
+    def ids_of_normalised(self, xn, codebook=None):
+        """the cosine argmax of unit-norm rows against the codebook (or another (V, dim) set of unit-norm rows: the k-means means)"""
         M, D = xn.shape
         V = self.codebook_size
-        cb = self.codebook.contiguous()
+        cb = (self.codebook if codebook is None else codebook).contiguous()
         zero_bias = torch.zeros((V,), device=xn.device, dtype=torch.float32)
         partials = torch.empty((5 * L.vocab_ntiles(V) * M,), device=xn.device, dtype=torch.float32)
         L.vocab_sample(L.F32, xn, cb, zero_bias, M, V, D, 1.0, None, None, 0, False, partials, no_noise=True)

@@ -18,6 +18,7 @@ forward and backward kernels, the PEG with causal frame padding); this file adds
     _VQFn           lookup_free_quantization=False: l2norm -> cosine argmax -> codebook    pk_l2norm_rows, pk_vocab_sample / pk_vocab_reduce,
                     row straight through, commitment loss, EMA codebook update           pk_vq_gather_commit / pk_vq_commit_bwd, pk_vq_hist / scan / fill /
                                                                                          codebook_update
+                    (+ dead-code expiry, k-means init, cross-rank statistics when on)    (pk_vq_scan_expire / codebook_update_expire / compact_keep / kmeans_means)
     _PatchMSE       mean (to_pixels(tokens) - patches(video))^2 -- un-patchify is a     pk_patchify_ln (raw rows), pk_sqdiff_partials
                     bijection of the pixels, so the loss is taken in patch layout        / pk_scaled_diff
 
@@ -222,13 +223,24 @@ def _warn_vq_statistics_per_rank():
         _WARNED_VQ_PER_RANK = True
 
 
+def _all_gather_rows(t, ws):
+    """(M, ...) on every rank -> (ws M, ...) in rank order: one all_gather_into_tensor on the default group (equal M on every rank)"""
+    import torch.distributed as dist
+    t = t.contiguous()
+    out = torch.empty((ws * t.shape[0], *t.shape[1:]), device=t.device, dtype=t.dtype)
+    dist.all_gather_into_tensor(out, t)
+    return out
+
+
 class _VQFn(torch.autograd.Function):
     """The cosine-sim `VectorQuantize` (quantize.py) in training mode -- the published module's semantics as restated in DESIGN.md "VectorQuantize
     training" (call site cvivit.py:568-570; parity with the un-vendored package unpinned).  x (M, D) f32 rows, keep (M,) bool or None:
         ids = argmax_c l2norm(x) . E[c] by the exact-f32 lookup of the inference path (the ids the tokenizer emits); every row gets one;
         y = E[ids], gathered BEFORE the update; backward dx = dy (straight through);
         commit = commitment_weight * mean over the kept rows of (y - x)^2, y detached: kept rows get d commit * w * 2 (x - y) / (n_keep D);
-        the EMA update of cluster_size / embed_avg / embed from the kept rows, in place, in every call (grad mode or not), never differentiated.
+        the EMA update of cluster_size / embed_avg / embed from the kept rows, in place, in every call (grad mode or not), never differentiated;
+        the module's upkeep where it is switched on (quantize.VectorQuantize): k-means initialisation before the lookup of the first call, dead-code
+        expiry inside the update, both over the rows of every rank when the statistics are synced (q, commit and dx stay this rank's own).
     Returns (y, ids), or (y, commit, ids) with want_commit; ids is not differentiable.  The backward pass reads the code rows back from y itself:
     the codebook has moved on by then."""
 
@@ -245,14 +257,32 @@ class _VQFn(torch.autograd.Function):
             n_keep = int(keep.sum().item())                          # (one host read per masked step: the divisor of the mean)
             if n_keep == 0:
                 raise ValueError('VectorQuantize training step: the mask keeps no row')
-        _warn_vq_statistics_per_rank()
+        ws = vq.sync_world()
+        if ws == 1:
+            _warn_vq_statistics_per_rank()
+        draws = vq.begin_upkeep()
         x = x.detach()
         xn = vq.normalised(x)
-        ids = vq.ids_of_normalised(xn)
         E = cb.embed[0]
+        # the rows the codebook statistics see: this rank's, or every rank's in rank order (all ones stand in for an absent mask)
+        data, dkeep = xn, keep
+        if ws > 1:
+            data = _all_gather_rows(xn, ws)
+            dkeep = _all_gather_rows(keep if keep is not None else torch.ones((M,), device=dev, dtype=torch.uint8), ws)
+        if draws['kmeans_b'] is not None:
+            L.vq_kmeans(data, dkeep, E, vq.kmeans_iters, draws['kmeans_b'], vq.ids_of_normalised, embed_avg=cb.embed_avg[0],
+                        cluster_size=cb.cluster_size[0])
+            vq.kmeans_done()
+        ids = vq.ids_of_normalised(xn)
         y, rowsq = _f32((M, D), dev), _f32((M,), dev)
         L.vq_gather_commit(x, E, ids, keep, y, rowsq)
-        L.vq_ema_update(xn, ids, keep, cb.cluster_size[0], cb.embed_avg[0], E, vq.decay, vq.eps)
+        dids = _all_gather_rows(ids, ws) if ws > 1 else ids
+        if draws['expire_b'] is not None:
+            threshold = float(vq.threshold_ema_dead_code)
+            reset = threshold if vq.reset_cluster_size is None else float(vq.reset_cluster_size)
+            L.vq_ema_update_expire(data, dids, dkeep, cb.cluster_size[0], cb.embed_avg[0], E, vq.decay, vq.eps, threshold, reset, draws['expire_b'])
+        else:
+            L.vq_ema_update(data, dids, dkeep, cb.cluster_size[0], cb.embed_avg[0], E, vq.decay, vq.eps)
         for buf in (cb.cluster_size, cb.embed_avg, cb.embed):
             torch.autograd.graph.increment_version(buf)             # the kernels wrote through raw pointers
         ctx.mark_non_differentiable(ids)
