@@ -11,10 +11,16 @@ DataLoader (data.py:177-265); without it synthetic videos stand in.  One process
     python examples/train_cvivit.py --steps 20 --small --gan
     python examples/train_cvivit.py --steps 20 --gan --vgg16 vgg16.pt
     python examples/train_cvivit.py --steps 20 --small --vq-kmeans-init --vq-dead-code 2
+    python examples/train_cvivit.py --steps 20 --small --ema --eval-every 10
 
 `--vq-kmeans-init` / `--vq-dead-code T` train the Phenaki paper's cosine-sim VectorQuantize tokenizer (lookup_free_quantization=False) with the
 published module's codebook upkeep: k-means initialisation from the first batch, and replacement of codes whose EMA cluster size fell below T.
 Under torchrun the codebook statistics are computed from every rank's rows (sync_codebook), so all ranks keep one codebook.
+
+`--eval-every N` is the validation step of the reference's trainer (cvivit_trainer.py:284-323, every save_results_every steps the EMA tokenizer
+reconstructs held-out clips) with numbers instead of image grids: every N steps rank 0 runs `--eval-batches` held-out batches through
+P.TokenizerMetrics (the EMA copy with `--ema`) and prints PSNR, SSIM, the number of codes in use and the perplexity of the code histogram.
+Under torchrun the validation is rank 0's alone (`compute(merge=False)`: no collective, the other ranks do not wait for it).
 """
 import argparse
 import contextlib
@@ -59,6 +65,9 @@ def main():
     ap.add_argument('--vq-kmeans-init', action='store_true', help='the cosine-sim VectorQuantize tokenizer, its codebook initialised by k-means on the first batch')
     ap.add_argument('--vq-dead-code', type=float, default=0., metavar='T', help='the cosine-sim VectorQuantize tokenizer with threshold_ema_dead_code = T: '
                     'a code whose EMA cluster size falls below T is replaced by a row of the batch')
+    ap.add_argument('--eval-every', type=int, default=0, metavar='N', help='every N steps rank 0 validates on held-out clips: PSNR, SSIM, codebook usage '
+                    '(the EMA tokenizer with --ema)')
+    ap.add_argument('--eval-batches', type=int, default=2, metavar='K', help='held-out batches per validation')
     args = ap.parse_args()
     ws = int(os.environ.get('WORLD_SIZE', '1'))
     if ws > 1:
@@ -107,6 +116,32 @@ def main():
         fixed = torch.rand(args.batch, 3, args.frames, size, size, device='cuda')
         stream = iter(lambda: fixed, None)
 
+    def held_out():
+        """--eval-batches held-out batches: a second pass over the folder in its own fixed order, or a second fixed synthetic clip"""
+        if args.folder:
+            g = torch.Generator().manual_seed(12345)
+            second = DataLoader(VideoDataset(args.folder, size, num_frames=args.frames), batch_size=args.batch, shuffle=True, drop_last=True, generator=g)
+            for i, (clip,) in enumerate(second):
+                if i >= args.eval_batches:
+                    break
+                yield clip.cuda()
+        else:
+            g = torch.Generator(device='cuda').manual_seed(12345)
+            clip = torch.rand(args.batch, 3, args.frames, size, size, device='cuda', generator=g)
+            for _ in range(args.eval_batches):
+                yield clip
+
+    def validate(step):
+        model = ema.ema_model if ema is not None else cvivit
+        tm = P.TokenizerMetrics(model)
+        for clip in held_out():
+            tm.update(clip)                                            # device-side sums only
+        # the one synchronisation.  merge=False: only rank 0 validates (it holds the only EMA copy) while the other ranks go on to their next step,
+        # so nothing may be sent here -- compute()'s default sums the state over the process group and is a collective every rank would have to join
+        r = tm.compute(merge=False)
+        print(f'eval: step {step:4d}  psnr {r["psnr"]:.2f} dB  ssim {r["ssim"]:.4f}  codes used {r["codes_used"]}/{r["codebook_size"]}  '
+              f'perplexity {r["perplexity"]:.1f}', flush=True)
+
     t0 = None
     for step in range(args.steps):
         if step == 3:
@@ -135,6 +170,8 @@ def main():
         if rank == 0 and (step % 5 == 0 or step == args.steps - 1):
             tail = f'  discriminator loss {float(discr_loss.detach()):.5f}' if discr_loss is not None else ''
             print(f'step {step:4d}  {"vae" if args.gan else "reconstruction"} loss {float(loss.detach()):.5f}{tail}', flush=True)
+        if rank == 0 and args.eval_every > 0 and (step + 1) % args.eval_every == 0:
+            validate(step + 1)
     torch.cuda.synchronize()
     if rank == 0 and t0 is not None and args.steps > 3:
         dt = (time.perf_counter() - t0) / (args.steps - 3)

@@ -593,6 +593,27 @@ int pk_maxpool2x2_bwd(int is_f32, const void* x, const float* dy, int B, int H, 
 int pk_adaptive_avgpool(int is_f32, const void* x, int B, int H, int W, int C, float* out, void* stream);
 int pk_adaptive_avgpool_bwd(const float* dy, int B, int H, int W, int C, float* dx, void* stream);
 
+/* ---- validation metrics of the tokenizer (csrc/metrics.hip; the reference's trainer only dumps image grids, cvivit_trainer.py:284-323).  a, b:
+ * contiguous f32 videos (B, C, F, H, W), 4-byte aligned (16-byte loads are used where the addresses allow them, the results do not depend on it);
+ * results per frame, (B, F) f32, the C planes of a frame combined.  clamp_hi > 0: the FIRST operand is read as min(max(a, 0), clamp_hi) (no copy is
+ * written); <= 0: as it is.  partials: planes x pk_frame_*_parts(H, W) doubles of workspace (nparts = that product), one slot per workgroup, added
+ * per frame in index order: no floating-point atomics, bit-reproducible.  Always f32 arithmetic, whatever the model's compute dtype.
+ *   pk_frame_sqerr: mse[b, f] = mean over C H W of (a - b)^2, any H, W >= 1; psnr (optional) = 10 log10(R^2 / max(mse, 1e-10 R^2)), R = data_range,
+ *                   formed from the unrounded mean (identical frames: exactly 100).
+ *   pk_frame_ssim:  SSIM of Wang et al. as pytorch-msssim / torchmetrics compute it: 11 x 11 Gaussian window (sigma 1.5, sum 1), 'valid' positions
+ *                   (H - 10) x (W - 10), biased moments, C1 = (0.01 R)^2, C2 = (0.03 R)^2, the map averaged over the positions and planes of the frame.
+ *                   H, W >= 11.  The moments are accumulated on a - s, b - s (s = the tile's mean of a), never as E[a^2] - E[a]^2 on raw pixels;
+ *                   identical frames give exactly 1.
+ *   pk_code_usage:  counts (V,) int32 as pk_vq_hist writes them -> out[0..5) doubles: total T, codes with count > 0, entropy H = -sum p ln p over p > 0
+ *                   (p = count / T), perplexity exp(H), max p.  T = 0: 0, 0, 0, 1, 0.  One workgroup, fixed-order sums. */
+int pk_frame_sqerr_parts(int H, int W);
+int pk_frame_ssim_parts(int H, int W);
+int pk_frame_sqerr(const float* a, const float* b, int B, int C, int F, int H, int W, float clamp_hi, float data_range, double* partials,
+                   long long nparts, float* mse, float* psnr, void* stream);
+int pk_frame_ssim(const float* a, const float* b, int B, int C, int F, int H, int W, float clamp_hi, float data_range, double* partials,
+                  long long nparts, float* ssim, void* stream);
+int pk_code_usage(const int* counts, int V, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

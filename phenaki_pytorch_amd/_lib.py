@@ -138,6 +138,11 @@ SIGNATURES = {
     'pk_maxpool2x2_bwd': [_I, _P, _P, _I, _I, _I, _I, _P, _P],
     'pk_adaptive_avgpool': [_I, _P, _I, _I, _I, _I, _P, _P],
     'pk_adaptive_avgpool_bwd': [_P, _I, _I, _I, _I, _P, _P],
+    'pk_frame_sqerr_parts': [_I, _I],
+    'pk_frame_ssim_parts': [_I, _I],
+    'pk_frame_sqerr': [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P, _P],
+    'pk_frame_ssim': [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P],
+    'pk_code_usage': [_P, _I, _P, _P],
 }
 
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
@@ -508,6 +513,51 @@ def vq_kmeans(data, keep, means, iters, b, lookup, *, embed_avg=None, cluster_si
             all_means.append(means.clone())
     out = (means, counts, torch.stack(all_ids))
     return out + (torch.stack(all_means),) if trace else out
+
+
+def frame_sqerr(a, b, clamp_hi=0., data_range=None):
+    """per-frame mean of (a - b)^2 over C H W of two contiguous f32 (B, C, F, H, W) videos -> mse (B, F) f32 [and, with data_range, psnr (B, F) f32].
+    clamp_hi > 0: the first operand is read clamped to [0, clamp_hi]."""
+    B, C, F, H, W = a.shape
+    lib = load()
+    parts = lib.pk_frame_sqerr_parts(H, W)
+    if parts < 0:
+        _check(parts, 'pk_frame_sqerr_parts')
+    partials = torch.empty((B * C * F * parts,), device=a.device, dtype=torch.float64)
+    mse = torch.empty((B, F), device=a.device, dtype=torch.float32)
+    psnr = torch.empty_like(mse) if data_range is not None else None
+    _check(lib.pk_frame_sqerr(f32p(a, 'a'), f32p(b, 'b'), B, C, F, H, W, float(clamp_hi), float(data_range or 0.), ptr(partials), partials.numel(),
+                              ptr(mse), ptr(psnr), stream(a)), 'pk_frame_sqerr')
+    return (mse, psnr) if psnr is not None else mse
+
+
+def frame_ssim(a, b, data_range=1., clamp_hi=0.):
+    """per-frame SSIM (11 x 11 Gaussian window, sigma 1.5, 'valid' positions) of two contiguous f32 (B, C, F, H, W) videos, H, W >= 11 -> (B, F) f32"""
+    B, C, F, H, W = a.shape
+    lib = load()
+    parts = lib.pk_frame_ssim_parts(H, W)
+    if parts < 0:
+        _check(parts, 'pk_frame_ssim_parts')
+    partials = torch.empty((B * C * F * parts,), device=a.device, dtype=torch.float64)
+    out = torch.empty((B, F), device=a.device, dtype=torch.float32)
+    _check(lib.pk_frame_ssim(f32p(a, 'a'), f32p(b, 'b'), B, C, F, H, W, float(clamp_hi), float(data_range), ptr(partials), partials.numel(), ptr(out),
+                             stream(a)), 'pk_frame_ssim')
+    return out
+
+
+def code_hist(ids, keep, V):
+    """counts (V,) int32 of the kept ids (pk_vq_hist; an id outside [0, V) is dropped on the device, nothing synchronises)"""
+    M = ids.numel()
+    counts = torch.zeros((V,), device=ids.device, dtype=torch.int32)
+    _check(load().pk_vq_hist(ptr(ids), ptr(keep), M, V, ptr(counts), 0, stream(ids)), 'pk_vq_hist')
+    return counts
+
+
+def code_usage(counts):
+    """(V,) int32 counts -> (5,) f64 on the device: total, used codes, entropy (nats), perplexity, largest share"""
+    out = torch.empty((5,), device=counts.device, dtype=torch.float64)
+    _check(load().pk_code_usage(ptr(counts), counts.numel(), ptr(out), stream(counts)), 'pk_code_usage')
+    return out
 
 
 def embed(ids, tok, pos, out, S, n, D, *, nb=None, ids_prime=None, out_t=None):

@@ -130,10 +130,14 @@ class CViViT(PackedModule):
         ph, pw = self.patch_size
         assert torch.all(((video_frame_mask.sum(dim=-1) - 1) % self.temporal_patch_size) == 0), \
             'number of frames must be divisible by temporal patch size, subtracting off the first frame'
+        return self._token_mask_of_frames(video_frame_mask, (h // ph) * (w // pw))
+
+    def _token_mask_of_frames(self, video_frame_mask, tokens_per_frame):
+        """calculate_video_token_mask without its assert (which reads the device): evaluate() must not synchronise"""
         first, rest = video_frame_mask[:, :1], video_frame_mask[:, 1:]
         rest = rest.reshape(rest.shape[0], -1, self.temporal_patch_size)
         video_mask = torch.cat((first, rest.any(dim=-1)), dim=-1)
-        return video_mask.repeat_interleave((h // ph) * (w // pw), dim=-1)
+        return video_mask.repeat_interleave(tokens_per_frame, dim=-1)
 
     def get_video_patch_shape(self, num_frames, include_first_frame=True):
         patch_frames = 0
@@ -525,3 +529,34 @@ class CViViT(PackedModule):
         if return_recons:
             return recon_loss, returned_recon
         return recon_loss
+
+    @torch.no_grad()
+    def evaluate(self, video, mask=None, data_range=1., clamp=True):
+        """the validation pass of the reference's trainer (cvivit_trainer.py:284-323 reconstructs held-out clips and dumps image grids) with numbers
+        (metrics.py): tokenize -> codes -> decode exactly as forward(..., return_recons_only=True), then per-frame MSE / PSNR / SSIM of the
+        reconstruction against the video and the codebook usage of the ids.  Always under no_grad; the module's training flag and the
+        VectorQuantize EMA buffers are not touched (the lookup and the decoder never read the flag), and nothing synchronises with the host:
+        every value of the returned dict is a device tensor --
+          ids (B, T', h, w) int64; mse, psnr, ssim (B, F) f32; mse_mean, psnr_mean, ssim_mean over the frames `mask` (B, F) keeps (all by
+          default) and frames, their number; codebook_usage: metrics.codebook_usage of the ids calculate_video_token_mask keeps.
+        clamp: the reconstruction is read clamped to [0, data_range] inside the metric kernels (no clamped copy is written)."""
+        from . import metrics as M
+        video = self._check_video(video, mask)
+        L.require_device(video, 'video')
+        video = video.float().contiguous()
+        b, c, f, *image_dims = video.shape
+        if exists(mask):
+            L.require_device(mask, 'mask')
+            if tuple(mask.shape) != (b, f):
+                raise ValueError(f'evaluate: mask must be (batch, frames) = ({b}, {f}), got {tuple(mask.shape)}')
+            mask = mask.bool()
+        ids = self.tokenize(video)
+        T = 1 + (f - 1) // self.temporal_patch_size
+        recon = self._decode2d(self.vq.codes_2d(ids.reshape(-1), perm=(T, self.image_num_tokens)), b, T, temporal_rows=True)
+        hi = data_range if clamp else None
+        mse, psnr = M._mse_psnr(recon, video, data_range, clamp=hi)
+        ssim = M.ssim(recon, video, data_range, clamp=hi)
+        keep = self._token_mask_of_frames(mask, self.image_num_tokens) if exists(mask) else None
+        frames = mask.sum() if exists(mask) else torch.full((), b * f, device=video.device, dtype=torch.int64)
+        return dict(ids=ids, mse=mse, psnr=psnr, ssim=ssim, mse_mean=M._masked_mean(mse, mask), psnr_mean=M._masked_mean(psnr, mask),
+                    ssim_mean=M._masked_mean(ssim, mask), frames=frames, codebook_usage=M.codebook_usage(ids, self.vq.codebook_size, keep=keep))
