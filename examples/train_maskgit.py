@@ -3,6 +3,7 @@ cross entropy + TokenCritic BCE) -> backward -> [gradient all-reduce] -> AdamW. 
 dataset and the T5 encoder; one process per GPU (`torchrun --nproc-per-node N examples/train_maskgit.py` averages gradients over RCCL).
 
     python examples/train_maskgit.py --steps 20 --dtype bf16x3
+    python examples/train_maskgit.py --steps 40 --eval-every 10 --eval-batches 2        # + held-out perplexity / top-k accuracy on rank 0
 """
 import argparse
 import os
@@ -25,6 +26,8 @@ def main():
     ap.add_argument('--attn-dropout', type=float, default=0., help='dropout on the attention probabilities of MaskGit and the critic (in training mode)')
     ap.add_argument('--ff-dropout', type=float, default=0., help='dropout behind GEGLU in their feed-forwards')
     ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm inside the AdamW update (phenaki_trainer.py:380-381)')
+    ap.add_argument('--eval-every', type=int, default=0, help='every N steps rank 0 runs --eval-batches held-out batches through MaskGitMetrics and prints one line')
+    ap.add_argument('--eval-batches', type=int, default=2)
     ap.add_argument('--save', default='')
     args = ap.parse_args()
     ws = int(os.environ.get('WORLD_SIZE', '1'))
@@ -54,6 +57,27 @@ def main():
     with torch.no_grad():
         ids = phenaki.cvivit(videos, return_only_codebook_ids=True)              # the tokenizer is frozen: encode once per batch
     reducer = P.GradientReducer(params, broadcast=False) if ws > 1 else None
+
+    def held_out():
+        """--eval-batches held-out batches of (ids, text embeddings): fixed synthetic clips of their own seed, tokenized once"""
+        g = torch.Generator(device='cuda').manual_seed(12345)
+        for _ in range(args.eval_batches):
+            clip = torch.randn(args.batch, 3, 17, size, size, device='cuda', generator=g)
+            emb = torch.randn(args.batch, 12, ctx_dim, device='cuda', generator=g)
+            with torch.no_grad():
+                yield phenaki.cvivit(clip, return_only_codebook_ids=True), emb
+
+    def validate(step):
+        mm = P.MaskGitMetrics(phenaki)
+        g = torch.Generator(device='cuda').manual_seed(54321)             # the mask draws: the held-out set is masked identically every time
+        for val_ids, val_emb in held_out():
+            mm.update(video_codebook_ids=val_ids, text_embeds=val_emb, generator=g)        # device-side sums only
+        # the one synchronisation.  merge=False: only rank 0 validates while the other ranks go on to their next step, so nothing may be sent
+        # here -- compute()'s default sums the state over the process group and is a collective every rank would have to join
+        r = mm.compute(merge=False)
+        print(f'eval: step {step:4d}  loss {r["loss"]:.4f}  perplexity {r["perplexity"]:.1f}  top1 {r["top1"]:.4f}  top5 {r["top5"]:.4f}  '
+              f'mean rank {r["mean_rank"]:.1f}  entropy {r["entropy"]:.3f}  critic accuracy {r["critic_accuracy"]:.4f}  ({r["tokens"]} tokens)', flush=True)
+
     t0 = None
     for step in range(args.steps):
         if step == 3:
@@ -68,6 +92,8 @@ def main():
         if step % 5 == 0 or step == args.steps - 1:
             norm = f'  grad norm {float(opt.last_grad_norm):.4f}' if opt.last_grad_norm is not None else ''
             print(f'step {step:4d}  loss {float(loss.detach()):.4f}{norm}', flush=True)
+        if rank == 0 and args.eval_every > 0 and (step + 1) % args.eval_every == 0:
+            validate(step + 1)
     torch.cuda.synchronize()
     if t0 is not None and args.steps > 3:
         dt = (time.perf_counter() - t0) / (args.steps - 3)

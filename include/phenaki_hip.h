@@ -380,7 +380,23 @@ int pk_vocab_reduce(const void* partials, int M, int V, const int* rows, const u
  * target logit is the dot product of row m of A with row targets[r] of W (+ bias) -- same A / W / bias as that call. */
 int pk_vocab_ce(int dtype, const void* partials, int M, int V, const void* A, int lda, const void* W, int ldw,
                 const float* bias, int D, const long long* targets, const int* rows, float* loss, float* lse_out, void* stream);
-/* lse_out ([M] f32 or NULL): logsumexp of every row, kept for the backward pass below.
+/* The validation statistics of the vocab head (what a MaskGIT-style model is judged by: masked-token perplexity, top-k accuracy, the rank
+ * of the true token, the entropy of the predictive distribution) in one pass over the vocabulary, again without the logits; same A / lda /
+ * W / ldw / bias / M / V / D / rows as pk_vocab_sample, no noise, no temperature, no atomics.  pk_vocab_eval first forms the target logit
+ * t[m] = A[m] . W[targets[r]] + bias[targets[r]] (r = rows ? rows[m] : m, the dot product of pk_vocab_ce), then runs the tiled 128 x 128
+ * vocabulary kernel with an epilogue that leaves per (row, tile) the plain arg-max (first maximum wins), max, sum exp(l - max),
+ * sum exp(l - max) l and `greater`, the number of columns v != targets[r], v < V, with l_v > t[m] -- the target's own column is left out by
+ * INDEX, its MFMA value and t[m] may differ in the last bits.  workspace: pk_vocab_eval_words(V) * M 4-byte words.
+ * pk_vocab_eval_reduce folds the tiles of that workspace in a fixed order into per-row outputs, each [M] or NULL: pred (arg-max), lse,
+ * nll = lse - t, rank = sum of `greater` (exact; top-k accuracy is rank < k) and entropy = lse - sum_v p_v l_v in nats.  Two calls on the
+ * same inputs agree bit for bit.  A target outside [0, V) reads no weight row: its nll is nan and its rank 0. */
+int pk_vocab_eval_words(int V);
+int pk_vocab_eval(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias, int M, int V, int D,
+                  const long long* targets, const int* rows, void* workspace, void* stream);
+int pk_vocab_eval_reduce(const void* workspace, int M, int V, long long* pred, float* lse, float* nll, int* rank, float* entropy,
+                         void* stream);
+
+/* pk_vocab_ce's lse_out ([M] f32 or NULL): logsumexp of every row, kept for the backward pass below.
  *
  * Backward of that cross entropy (first training kernel; phenaki_pytorch.py:640-643 under autograd), one slab of
  * Vs vocabulary columns [v0, v0 + Vs) at a time: logits [M][ldl] f32 holds the slab's recomputed logits (pk_gemm of the same A / W rows

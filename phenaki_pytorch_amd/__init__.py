@@ -14,7 +14,8 @@ from .step_tail import clip_grad_norm_, EMA
 from .vgg import VGG16Features
 from . import metrics
 from .metrics import frame_mse, psnr, ssim, codebook_usage, TokenizerMetrics
+from .maskgit_metrics import MaskGitMetrics
 
 __all__ = ['CViViT', 'MaskGit', 'TokenCritic', 'SelfCritic', 'Phenaki', 'make_video', 'set_compute_dtype', 'invalidate_packed',
            'shard_batch', 'sample_sharded', 'make_video_sharded', 'vocab_cross_entropy', 'all_reduce_gradients', 'GradientReducer', 'broadcast_parameters', 'broadcast_module', 'HipAdamW', 'get_optimizer', 'clip_grad_norm_', 'EMA', 'VGG16Features',
-           'metrics', 'frame_mse', 'psnr', 'ssim', 'codebook_usage', 'TokenizerMetrics']
+           'metrics', 'frame_mse', 'psnr', 'ssim', 'codebook_usage', 'TokenizerMetrics', 'MaskGitMetrics']

@@ -81,6 +81,9 @@ SIGNATURES = {
     'pk_vocab_sample': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _ULL, _P, _I, _P, _P],
     'pk_vocab_reduce': [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     'pk_vocab_ce': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
+    'pk_vocab_eval_words': [_I],
+    'pk_vocab_eval': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
+    'pk_vocab_eval_reduce': [_P, _I, _I, _P, _P, _P, _P, _P, _P],
     'pk_ce_grad_slab': [_I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P],
     'pk_topk_mask': [_P, _I, _I, _I, _LL, _P, _P, _P, _P, _P],
     'pk_critic_head': [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _F, _ULL, _P, _P, _P],
@@ -707,6 +710,49 @@ def vocab_ce(dtype, partials, M, V, A, W, bias, D, targets, rows, loss, lse=None
     rc = load().pk_vocab_ce(dtype, ptr(partials), M, V, ptr(A), A.stride(-2), ptr(W), W.stride(0), f32p(bias, 'to_logits.bias'), D,
                             ptr(targets), ptr(rows), ptr(loss), ptr(lse), stream(A))
     _check(rc, 'pk_vocab_ce')
+
+
+def vocab_eval_words(M, V):
+    """4-byte words of workspace vocab_eval needs for M rows of a V-way head"""
+    return load().pk_vocab_eval_words(V) * M
+
+
+def vocab_eval(dtype, A, W, bias, M, V, D, targets, rows, *, pred=None, lse=None, nll=None, rank=None, entropy=None, workspace=None):
+    """validation statistics of the vocab head in one pass over the vocabulary, no logits written (pk_vocab_eval + pk_vocab_eval_reduce, see the
+    header).  A / W / bias / rows as vocab_sample; targets int64, indexed by rows[m] (or m) as in vocab_ce.  Outputs, each (M,) on the device or
+    None (not computed): pred int64 (arg-max), lse / nll / entropy f32 (nats), rank int32 (columns other than the target with a larger logit:
+    top-k is rank < k).  workspace: f32, >= vocab_eval_words(M, V) elements, allocated here unless given (a captured graph keeps its own)."""
+    if dtype not in (F32, BF16, BF16X3):
+        raise ValueError(f'vocab_eval: unknown compute dtype {dtype}')
+    if A.dtype != tdtype(dtype) or A.ndim != 2 or A.stride(-1) != 1 or A.shape[0] < M:
+        raise ValueError(f'vocab_eval: A must be (>= {M}, D) {tdtype(dtype)} with unit column stride, got {tuple(A.shape)} {A.dtype}')
+    if W.dtype != tdtype(dtype) or W.ndim != 2 or W.stride(-1) != 1 or W.shape[0] < V:
+        raise ValueError(f'vocab_eval: W must be (>= {V}, K) {tdtype(dtype)} with unit column stride, got {tuple(W.shape)} {W.dtype}')
+    if targets.dtype != torch.int64 or not targets.is_contiguous() or (rows is None and targets.numel() < M):
+        raise ValueError(f'vocab_eval: targets must be contiguous int64 with an entry per logical row, got {tuple(targets.shape)} {targets.dtype}')
+    if rows is not None and (rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() < M or rows.device != A.device):
+        raise ValueError(f'vocab_eval: rows must be {M} contiguous int32 on {A.device}, got {tuple(rows.shape)} {rows.dtype} on {rows.device}')
+    outs = (('pred', pred, torch.int64), ('lse', lse, torch.float32), ('nll', nll, torch.float32), ('rank', rank, torch.int32),
+            ('entropy', entropy, torch.float32))
+    for name, t, want in outs:
+        if t is not None and (t.dtype != want or not t.is_contiguous() or t.numel() < M or t.device != A.device):
+            raise ValueError(f'vocab_eval: {name} must be {M} contiguous {want} on {A.device}, got {tuple(t.shape)} {t.dtype} on {t.device}')
+    if targets.device != A.device or W.device != A.device:
+        raise ValueError(f'vocab_eval: operands on {A.device}, {W.device} and {targets.device}')
+    for t, name in ((A, 'A'), (W, 'W'), (targets, 'targets')):
+        require_device(t, name)
+    words = vocab_eval_words(M, V)
+    if workspace is None:
+        workspace = torch.empty((words,), device=A.device, dtype=torch.float32)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() < words or workspace.device != A.device:
+        raise ValueError(f'vocab_eval: workspace must be >= {words} contiguous float32 on {A.device}')
+    lib = load()
+    rc = lib.pk_vocab_eval(dtype, ptr(A), A.stride(-2), ptr(W), W.stride(0), f32p(bias, 'to_logits.bias'), M, V, D, ptr(targets), ptr(rows),
+                           ptr(workspace), stream(A))
+    _check(rc, 'pk_vocab_eval')
+    rc = lib.pk_vocab_eval_reduce(ptr(workspace), M, V, ptr(pred), ptr(lse), ptr(nll), ptr(rank), ptr(entropy), stream(A))
+    _check(rc, 'pk_vocab_eval_reduce')
+    return workspace
 
 
 def ce_grad_slab(logits, lse, targets, rows, M, Vs, v0, scale, g, gT, db=None, scale_dev=None):

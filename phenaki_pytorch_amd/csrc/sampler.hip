@@ -65,42 +65,47 @@ template <typename T> struct VocabGeom { static constexpr int TM = 4, TN = 2, WM
 template <> struct VocabGeom<bf16x3> { static constexpr int TM = 4, TN = 4, WM = 2, WN = 2; };
 template <typename T> using VocabTile = GemmDma<T, VocabGeom<T>::TM, VocabGeom<T>::TN, VocabGeom<T>::WM, VocabGeom<T>::WN, 2>;
 
+// ---- XCD-aware, L2-panelled tile order of the 1-D grid of 8 * ceil(ntiles / 8) * MT workgroups (MT row tiles), shared by the sampling and the
+// evaluation kernel.  Workgroup b is observed to run on XCD b % 8 (speed only).  XCD x owns a contiguous
+// eighth of the vocabulary tiles (its slice of W: 8.4 MB at V = 65 536) and walks it in W-panels of 16 tiles (2 MB) x A-panels of
+// 8 row tiles (1 MB), rows fastest: both panels stay in the XCD's 4 MB L2 while their 128 tiles run.  The former (row tile, vocab
+// tile) grid in dispatch order spread every vocabulary tile's row tiles over all 8 XCDs: each L2 then cycled through the WHOLE of A
+// (4.7 MB at 4608 rows) once per vocabulary tile and fetched every W tile 8 times.
+// false: this workgroup owns no tile (ntiles % 8 != 0, or ntiles < 8 where some XCD slices are empty) and returns before any barrier.
+__device__ __forceinline__ bool vocab_tile_of_block(int MT, int ntiles, int plain_order, int& mtile, int& ntile) {
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    const int cn = (ntiles + 7) / 8;
+    const int nstart = xcd * ntiles / 8, ncount = (xcd + 1) * ntiles / 8 - nstart;
+    if (plain_order) {
+        mtile = (int)(blockIdx.x % (unsigned)MT); ntile = (int)(blockIdx.x / (unsigned)MT);
+        return ntile < ntiles;
+    }
+    constexpr int PN = 16, PM = 8;
+    const int full_wp = cn / PN;
+    int wp = idx / (PN * MT);
+    if (wp > full_wp) wp = full_wp;
+    const int basen = wp * PN, pnl = wp < full_wp ? PN : cn - basen;
+    const int r = idx - wp * PN * MT;
+    const int full_ap = MT / PM;
+    int ap = r / (pnl * PM);
+    if (ap > full_ap) ap = full_ap;
+    const int basem = ap * PM, pml = ap < full_ap ? PM : MT - basem;
+    const int r2 = r - ap * pnl * PM;
+    mtile = basem + r2 % pml;
+    ntile = basen + r2 / pml;
+    if (ntile >= ncount) return false;
+    ntile += nstart;
+    return true;
+}
+
 template <typename T, bool PARITY, bool LSE>
 __global__ __launch_bounds__(64 * VocabGeom<T>::WM * VocabGeom<T>::WN) void vocab_sample_kernel(const GemmOperands p, const VocabArgs e) {
     using Tile = VocabTile<T>;
     constexpr int VTM = VocabGeom<T>::TM, VTN = VocabGeom<T>::TN, VWN = VocabGeom<T>::WN;
     static_assert(Tile::BM == 128 && Tile::BN == 128, "partials are laid out per 128-column tile");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // ---- XCD-aware, L2-panelled tile order.  Workgroup b is observed to run on XCD b % 8 (speed only).  XCD x owns a contiguous
-    // eighth of the vocabulary tiles (its slice of W: 8.4 MB at V = 65 536) and walks it in W-panels of 16 tiles (2 MB) x A-panels of
-    // 8 row tiles (1 MB), rows fastest: both panels stay in the XCD's 4 MB L2 while their 128 tiles run.  The former (row tile, vocab
-    // tile) grid in dispatch order spread every vocabulary tile's row tiles over all 8 XCDs: each L2 then cycled through the WHOLE of A
-    // (4.7 MB at 4608 rows) once per vocabulary tile and fetched every W tile 8 times.
-    const int MT = (p.M + Tile::BM - 1) / Tile::BM;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int cn = (e.ntiles + 7) / 8;
-    const int nstart = xcd * e.ntiles / 8, ncount = (xcd + 1) * e.ntiles / 8 - nstart;
     int mtile, ntile;
-    if (e.plain_order) {
-        mtile = (int)(blockIdx.x % (unsigned)MT); ntile = (int)(blockIdx.x / (unsigned)MT);
-        if (ntile >= e.ntiles) return;
-    } else {
-        constexpr int PN = 16, PM = 8;
-        const int full_wp = cn / PN;
-        int wp = idx / (PN * MT);
-        if (wp > full_wp) wp = full_wp;
-        const int basen = wp * PN, pnl = wp < full_wp ? PN : cn - basen;
-        const int r = idx - wp * PN * MT;
-        const int full_ap = MT / PM;
-        int ap = r / (pnl * PM);
-        if (ap > full_ap) ap = full_ap;
-        const int basem = ap * PM, pml = ap < full_ap ? PM : MT - basem;
-        const int r2 = r - ap * pnl * PM;
-        mtile = basem + r2 % pml;
-        ntile = basen + r2 / pml;
-        if (ntile >= ncount) return;                       // whole workgroup exits before any barrier
-        ntile += nstart;
-    }
+    if (!vocab_tile_of_block((p.M + Tile::BM - 1) / Tile::BM, e.ntiles, e.plain_order, mtile, ntile)) return;   // whole workgroup exits before any barrier
     const int m0 = mtile * Tile::BM, n0 = ntile * Tile::BN;
     f32x4 acc[VTM][VTN];
 #pragma unroll
@@ -613,6 +618,209 @@ __global__ __launch_bounds__(256) void vocab_ce_kernel(const float* __restrict__
     }
 }
 
+// ---- pk_vocab_eval: the validation statistics of the vocab head in ONE pass over the vocabulary, still without the logits ----------------------
+// Per row: arg-max, log-sum-exp, the target's negative log-likelihood, the target's RANK (number of other columns with a larger logit: top-k
+// accuracy for any k is rank < k) and the entropy of the predictive distribution, H = lse - sum_v p_v l_v.  The (max, sum exp) partials of
+// pk_vocab_sample give the first three; rank and entropy need their own epilogue over the same MFMA product:
+//   1. vocab_target_logit_kernel: t[m] = A[m] . W[targets[r]] + bias, the dot product vocab_ce_kernel forms, from the same operand images;
+//   2. vocab_eval_kernel: the 128 x 128 tile of vocab_sample_kernel (same main loop, same tile order), whose epilogue leaves per (row, tile)
+//      (arg-max, max, sum exp(l - max), sum exp(l - max) l, #{v != target : l_v > t});
+//   3. vocab_eval_reduce_kernel: folds the tiles per row.
+// No noise, no temperature, no atomics: every output is a fixed-order function of the inputs (two calls agree bit for bit).
+struct VocabEvalArgs {
+    const float* bias;           // [V]
+    const int* rows;             // optional: output row m is logical row rows[m] (indexes targets)
+    const long long* targets;    // [logical rows]
+    const float* tlogit;         // [M] target logits of pass 1
+    int ntiles;
+    // partials, SoA [ntiles][M]
+    int* p_idx; float* p_max; float* p_sum; float* p_sl; int* p_gt;
+};
+
+// one wave per row; a target outside [0, V) reads no weight row and gives t = nan (nll nan, rank 0)
+template <typename T>
+__global__ __launch_bounds__(256) void vocab_target_logit_kernel(const T* __restrict__ A, int lda, const T* __restrict__ W, int ldw,
+                                                                 const float* __restrict__ bias, int M, int V, int D,
+                                                                 const long long* __restrict__ targets, const int* __restrict__ rows,
+                                                                 float* __restrict__ tlogit) {
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const long long tgt = targets[rows ? rows[m] : m];
+    if (tgt < 0 || tgt >= V) {
+        if (lane == 0) tlogit[m] = __builtin_nanf("");
+        return;
+    }
+    const T* a = A + (size_t)m * lda;
+    const T* w = W + (size_t)tgt * ldw;
+    float dot = 0.f;
+    for (int c = lane; c < D; c += 64) dot += load_elem(a + c) * w_elem<T>(w, c);
+    dot = wave_sum(dot);
+    if (lane == 0) tlogit[m] = dot + bias[tgt];
+}
+
+// (max, sum exp(l - max), sum exp(l - max) l) of two column sets -> of their union; an empty set has max = -inf and is skipped
+__device__ __forceinline__ void lse_merge(float& lmax, float& lsum, float& lsl, float om, float os, float ol) {
+    const float nm = fmaxf(lmax, om);
+    const float fa = lmax == -INFINITY ? 0.f : __expf(lmax - nm), fb = om == -INFINITY ? 0.f : __expf(om - nm);
+    lsum = (lmax == -INFINITY ? 0.f : lsum * fa) + (om == -INFINITY ? 0.f : os * fb);
+    lsl = (lmax == -INFINITY ? 0.f : lsl * fa) + (om == -INFINITY ? 0.f : ol * fb);
+    lmax = nm;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * VocabGeom<T>::WM * VocabGeom<T>::WN) void vocab_eval_kernel(const GemmOperands p, const VocabEvalArgs e) {
+    using Tile = VocabTile<T>;
+    constexpr int VTM = VocabGeom<T>::TM, VTN = VocabGeom<T>::TN, VWN = VocabGeom<T>::WN;
+    static_assert(Tile::BM == 128 && Tile::BN == 128, "partials are laid out per 128-column tile");
+    // LDS scratch of the epilogue, in the GEMM stages that are dead after run()'s final barrier: [wn][128 rows][5 words] = 10 240 bytes with
+    // 4 column waves (5 120 with the 2 x 2 layout of split-bf16).  Five words as in the sampling epilogue: without noise the best value IS the
+    // maximum, so (index, max, sum exp, sum exp l, greater) take the place of (best, index, logit, max, sum exp).
+    static_assert(VWN * 128 * 5 * sizeof(float) <= Tile::SMEM, "epilogue scratch lives inside the GEMM stages");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int mtile, ntile;
+    if (!vocab_tile_of_block((p.M + Tile::BM - 1) / Tile::BM, e.ntiles, 0, mtile, ntile)) return;   // whole workgroup exits before any barrier
+    const int m0 = mtile * Tile::BM, n0 = ntile * Tile::BN;
+    f32x4 acc[VTM][VTN];
+#pragma unroll
+    for (int i = 0; i < VTM; ++i)
+#pragma unroll
+        for (int j = 0; j < VTN; ++j) acc[i][j] = f32x4{0, 0, 0, 0};
+    (void)Tile::run(p, p.M, m0, n0, smem, acc);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave / VWN, wn = wave % VWN, g = lane >> 4, lr = lane & 15;
+    float* red = reinterpret_cast<float*>(smem);
+    const int V = p.N;
+    f32x4 bvj[VTN];
+#pragma unroll
+    for (int j = 0; j < VTN; ++j) {
+        const int n = n0 + wn * 16 * VTN + j * 16 + g * 4;
+        bvj[j] = n < V ? *reinterpret_cast<const f32x4*>(e.bias + n) : f32x4{0, 0, 0, 0};         // V % 4 == 0 (host check)
+    }
+    // the target's logit and column of the lane's rows, loaded ahead of the row-block loop; a row past M compares against +inf / column -1
+    float tval[VTM];
+    int tcol[VTM];
+#pragma unroll
+    for (int i = 0; i < VTM; ++i) {
+        const int m = m0 + wm * 16 * VTM + i * 16 + lr;
+        const bool mok = m < p.M;
+        tval[i] = mok ? e.tlogit[m] : INFINITY;
+        tcol[i] = mok ? (int)e.targets[e.rows ? e.rows[m] : m] : -1;
+    }
+#pragma unroll
+    for (int i = 0; i < VTM; ++i) {
+        const int ml = wm * 16 * VTM + i * 16 + lr;
+        float lmax = -INFINITY;
+        int bidx = 0x7fffffff, gt = 0;
+        float lg[4 * VTN];
+#pragma unroll
+        for (int j = 0; j < VTN; ++j) {
+            const int n = n0 + wn * 16 * VTN + j * 16 + g * 4;
+            const f32x4 bv = bvj[j];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int nn = n + r;
+                const float logit = acc[i][j][r] + bv[r];
+                const bool ok = nn < V;                                      // padding columns of the V tail count for nothing
+                lg[j * 4 + r] = ok ? logit : -INFINITY;
+                if (ok && logit > lmax) { lmax = logit; bidx = nn; }         // ascending nn: first maximum wins
+                // the target's own column is left out BY INDEX: its MFMA value and t may differ in the last bits
+                gt += (ok && nn != tcol[i] && logit > tval[i]) ? 1 : 0;
+            }
+        }
+        float lsum = 0.f, lsl = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4 * VTN; ++q) {
+            const float ex = __expf(lg[q] - lmax);                           // exp(-inf) = 0 for padding; lmax = -inf: discarded by lse_merge
+            lsum += ex;
+            lsl = fmaf(ex, fmaxf(lg[q], -3.0e38f), lsl);                     // 0 * (-inf) would be nan
+        }
+        // combine the 4 lane groups holding the same row
+#pragma unroll
+        for (int off = 16; off <= 32; off <<= 1) {
+            const float om = __shfl_xor(lmax, off, 64), os = __shfl_xor(lsum, off, 64), ol = __shfl_xor(lsl, off, 64);
+            const int oi = __shfl_xor(bidx, off, 64);
+            gt += __shfl_xor(gt, off, 64);
+            if (om > lmax || (om == lmax && oi < bidx)) bidx = oi;
+            lse_merge(lmax, lsum, lsl, om, os, ol);
+        }
+        if (g == 0) {
+            float* rr = red + ((size_t)wn * 128 + ml) * 5;
+            rr[0] = __builtin_bit_cast(float, bidx); rr[1] = lmax; rr[2] = lsum; rr[3] = lsl; rr[4] = __builtin_bit_cast(float, gt);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        const int ml = threadIdx.x, m = m0 + ml;
+        if (m < p.M) {
+            const float* a = red + (size_t)ml * 5;
+            int bidx = __builtin_bit_cast(int, a[0]), gt = __builtin_bit_cast(int, a[4]);
+            float lmax = a[1], lsum = a[2], lsl = a[3];
+#pragma unroll
+            for (int q = 1; q < VWN; ++q) {
+                const float* b = red + ((size_t)q * 128 + ml) * 5;
+                const int oi = __builtin_bit_cast(int, b[0]);
+                if (b[1] > lmax || (b[1] == lmax && oi < bidx)) bidx = oi;
+                gt += __builtin_bit_cast(int, b[4]);
+                lse_merge(lmax, lsum, lsl, b[1], b[2], b[3]);
+            }
+            const size_t o = (size_t)ntile * p.M + m;
+            e.p_idx[o] = bidx; e.p_max[o] = lmax; e.p_sum[o] = lsum; e.p_sl[o] = lsl; e.p_gt[o] = gt;
+        }
+    }
+}
+
+// fold the per-tile partials of vocab_eval_kernel: the layout of vocab_reduce_kernel (32 consecutive rows per workgroup, 8 thread groups
+// striding over the tiles, 8 loads in flight, meeting in LDS); outputs are indexed by the row m, like the loss of pk_vocab_ce
+__global__ __launch_bounds__(256) void vocab_eval_reduce_kernel(const int* __restrict__ p_idx, const float* __restrict__ p_max,
+                                                                const float* __restrict__ p_sum, const float* __restrict__ p_sl,
+                                                                const int* __restrict__ p_gt, const float* __restrict__ tlogit, int ntiles, int M,
+                                                                long long* __restrict__ pred, float* __restrict__ lse_out, float* __restrict__ nll,
+                                                                int* __restrict__ rank, float* __restrict__ entropy) {
+    __shared__ float red[8][32][5];
+    const int rr = threadIdx.x & 31, tg = threadIdx.x >> 5;
+    const int m = blockIdx.x * 32 + rr;
+    float lmax = -INFINITY, lsum = 0.f, lsl = 0.f;
+    int bidx = 0x7fffffff, gt = 0;
+    if (m < M) {
+        for (int t0 = tg; t0 < ntiles; t0 += 64) {
+            float om[8], os[8], ol[8];
+            int ix[8], og[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int t = t0 + u * 8;
+                const size_t o = (size_t)(t < ntiles ? t : tg) * M + m;
+                ix[u] = p_idx[o]; om[u] = p_max[o]; os[u] = p_sum[o]; ol[u] = p_sl[o]; og[u] = p_gt[o];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (t0 + u * 8 >= ntiles) break;
+                if (om[u] > lmax || (om[u] == lmax && ix[u] < bidx)) bidx = ix[u];
+                gt += og[u];
+                lse_merge(lmax, lsum, lsl, om[u], os[u], ol[u]);
+            }
+        }
+    }
+    red[tg][rr][0] = __builtin_bit_cast(float, bidx); red[tg][rr][1] = lmax; red[tg][rr][2] = lsum; red[tg][rr][3] = lsl;
+    red[tg][rr][4] = __builtin_bit_cast(float, gt);
+    __syncthreads();
+    if (tg != 0 || m >= M) return;
+    for (int q = 1; q < 8; ++q) {
+        const float om = red[q][rr][1];
+        const int ix = __builtin_bit_cast(int, red[q][rr][0]);
+        if (om > lmax || (om == lmax && ix < bidx)) bidx = ix;
+        gt += __builtin_bit_cast(int, red[q][rr][4]);
+        lse_merge(lmax, lsum, lsl, om, red[q][rr][2], red[q][rr][3]);
+    }
+    const float lse = lmax + logf(lsum);
+    if (pred) pred[m] = bidx;
+    if (lse_out) lse_out[m] = lse;
+    if (nll) nll[m] = lse - tlogit[m];
+    if (rank) rank[m] = gt;
+    if (entropy) entropy[m] = lse - lsl / lsum;
+}
+
 // ---- backward of that cross entropy, one SLAB of vocabulary columns at a time (the first training kernel, SURVEY.md 8f row 1;
 // reference phenaki_pytorch.py:640-643 under autograd): with loss = mean_m (lse_m - logit[m][t_m]) over the M rows,
 //     g[m][v] = d loss / d logit[m][v] = (exp(logit[m][v] - lse_m) - [v == t_m]) * scale,      scale = upstream gradient / M,
@@ -852,6 +1060,55 @@ extern "C" int pk_vocab_ce(int dtype, const void* partials, int M, int V, const 
                                        reinterpret_cast<const bf16*>(A), lda, reinterpret_cast<const bf16*>(W), ldw, bias, D, targets, rows, loss, lse_out);
     else hipLaunchKernelGGL((vocab_ce_kernel<float>), grid, dim3(256), 0, STREAM(stream), f + 3 * sz, f + 4 * sz, ntiles, M,
                             reinterpret_cast<const float*>(A), lda, reinterpret_cast<const float*>(W), ldw, bias, D, targets, rows, loss, lse_out);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+// workspace of pk_vocab_eval in 4-byte words PER ROW: the target logit + 5 partial arrays of ntiles words; layout [M | 5 x ntiles * M]
+extern "C" int pk_vocab_eval_words(int V) { return 1 + 5 * pk_vocab_ntiles(V); }
+
+extern "C" int pk_vocab_eval(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias, int M, int V, int D,
+                             const long long* targets, const int* rows, void* workspace, void* stream) {
+    if (!A || !W || !bias || !targets || !workspace || M <= 0 || V <= 0 || D <= 0) return PK_EINVAL;
+    if (dtype != 0 && dtype != 1 && dtype != 2) return PK_EINVAL;
+    const int eps = dtype == 1 ? 8 : 4;
+    if ((V & 3) || (D % eps) || (lda % eps) || (ldw % eps) || !al16(A) || !al16(W) || !al16(bias)) return PK_EALIGN;
+    const int ntiles = pk_vocab_ntiles(V);
+    const int bk = dtype == 1 ? 64 : 32;                  // LDS-DMA main loop: W zero-padded along K to the k-tile
+    if (ldw < (D + bk - 1) / bk * bk) return PK_EINVAL;
+    if ((size_t)M * lda * (dtype == 1 ? 2 : 4) >= 0xFFFFFFF0ull || (size_t)V * ldw * (dtype == 1 ? 2 : 4) >= 0xFFFFFFF0ull) return PK_EINVAL;
+    GemmOperands p{A, W, nullptr, lda, ldw, M, V, D, 0, krot_default()};
+    const size_t sz = (size_t)ntiles * M;
+    float* tl = reinterpret_cast<float*>(workspace);
+    VocabEvalArgs e;
+    e.bias = bias; e.rows = rows; e.targets = targets; e.tlogit = tl; e.ntiles = ntiles;
+    e.p_idx = reinterpret_cast<int*>(tl + M);
+    e.p_max = tl + M + sz; e.p_sum = tl + M + 2 * sz; e.p_sl = tl + M + 3 * sz;
+    e.p_gt = reinterpret_cast<int*>(tl + M + 4 * sz);
+    const dim3 tgrid((M + 3) / 4), grid(8 * ((ntiles + 7) / 8) * ((M + 127) / 128));        // 1-D: see vocab_tile_of_block
+    hipStream_t s = STREAM(stream);
+    // the target logits are written by the first launch and read by the second on the same stream
+#define PK_VE(TT) do { \
+        hipLaunchKernelGGL((vocab_target_logit_kernel<TT>), tgrid, dim3(256), 0, s, reinterpret_cast<const TT*>(A), lda, \
+                           reinterpret_cast<const TT*>(W), ldw, bias, M, V, D, targets, rows, tl); \
+        hipLaunchKernelGGL((vocab_eval_kernel<TT>), grid, dim3(VocabTile<TT>::THREADS), VocabTile<TT>::SMEM, s, p, e); } while (0)
+    if (dtype == 1) PK_VE(bf16);
+    else if (dtype == 2) PK_VE(bf16x3);                   // split-bf16: f32 rows of A, host-packed (hi | lo) planes of W (common.hpp)
+    else PK_VE(float);
+#undef PK_VE
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_vocab_eval_reduce(const void* workspace, int M, int V, long long* pred, float* lse, float* nll, int* rank, float* entropy,
+                                    void* stream) {
+    if (!workspace || M <= 0 || V <= 0) return PK_EINVAL;
+    const int ntiles = pk_vocab_ntiles(V);
+    const size_t sz = (size_t)ntiles * M;
+    const float* tl = reinterpret_cast<const float*>(workspace);
+    hipLaunchKernelGGL(vocab_eval_reduce_kernel, dim3((M + 31) / 32), dim3(256), 0, STREAM(stream),
+                       reinterpret_cast<const int*>(tl + M), tl + M + sz, tl + M + 2 * sz, tl + M + 3 * sz,
+                       reinterpret_cast<const int*>(tl + M + 4 * sz), tl, ntiles, M, pred, lse, nll, rank, entropy);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

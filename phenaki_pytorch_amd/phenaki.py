@@ -396,24 +396,16 @@ class Phenaki(PackedModule):
             return phenaki_loss(self, *args, **kwargs)
         return self.objective_value(*args, **kwargs)
 
-    @torch.no_grad()
-    def objective_value(self, videos=None, *, texts=None, video_codebook_ids=None, video_frame_mask=None, text_embeds=None,
-                        cond_drop_prob=None, only_train_generator=False, only_train_critic=False, _draws=None):
-        """phenaki_pytorch.py:562-687 -- the VALUE of the training objective (masked-token cross entropy + weighted
-        token-critic BCE).  Forward only: the result carries no autograd graph (the backward kernels are SURVEY.md 8f
-        "next").  The 65 536-way logits are never written: pk_vocab_sample draws the critic's input ids and leaves the
-        softmax statistics, pk_vocab_ce turns them into per-row losses.  As in the reference, `cond_drop_prob` has no
-        effect on this path (it is shadowed by `cond_drop_prob = 0` at :594).
-        _draws (tests): dict(rand_step (b,), perm_noise (b,n) U[0,1), gumbel_u (b,n,V) U[0,1)) replaces the three
-        random draws of the reference (:620, :626 -> :43-55, :653)."""
-        assert not (only_train_generator and only_train_critic)
-        assert not (only_train_critic and not exists(self.critic)), 'only_train_critic needs a critic (Phenaki(critic=...) or self_token_critic=True)'
+    def _masked_batch(self, videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws, mask_prob=None, generator=None):
+        """the inputs of the training call -> (ids (b, n) int64, patch shape, text_embeds, text_mask, video_mask, mask (b, n) bool, masked ids): the
+        tokenizer / text-encoder front end and the masking of phenaki_pytorch.py:580-628, shared by objective_value and evaluate.  The two draws
+        (schedule step, permutation noise) come from `draws` where it has them, else from `generator` (None: the device's default generator);
+        mask_prob replaces the cosine schedule by a fixed fraction."""
         assert exists(videos) ^ exists(video_codebook_ids), 'either raw video or video codebook ids must be given'
         assert not (exists(videos) and not exists(self.cvivit)), 'cvivit must be provided if one wants to encode the videos live during training'
         assert (exists(text_embeds) ^ exists(texts)) ^ self.unconditional, \
             'either raw text of text embeds must be given, and if unconditional, none should be given'
         assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), 'text embedding dimension is not correct'
-        mg, critic = self.maskgit, self.critic
         if not exists(video_codebook_ids):
             assert videos.ndim in {4, 5}
             if videos.ndim == 4:
@@ -437,18 +429,41 @@ class Phenaki(PackedModule):
 
         ids = video_codebook_ids.reshape(video_codebook_ids.shape[0], -1).long().contiguous()
         b, n = ids.shape
-        draws = _draws or {}
-        rand_step = draws['rand_step'].to(device) if 'rand_step' in draws else torch.randint(0, self.steps, (b,), device=device)
-        mask_token_prob = torch.cos(rand_step * math.pi * 0.5 / self.steps)
+        if exists(mask_prob):
+            mask_token_prob = torch.full((b,), float(mask_prob), device=device)
+        else:
+            rand_step = (draws['rand_step'].to(device) if 'rand_step' in draws
+                         else torch.randint(0, self.steps, (b,), device=device, generator=generator))
+            mask_token_prob = torch.cos(rand_step * math.pi * 0.5 / self.steps)
         vm = video_mask if exists(video_mask) else torch.ones((b, n), device=device, dtype=torch.bool)
         # get_mask_subset_with_prob (phenaki_pytorch.py:43-55)
         num_tokens = vm.sum(dim=-1)
         num_masked = (mask_token_prob * num_tokens).round().clamp(min=1)
-        perm_noise = draws['perm_noise'].to(device) if 'perm_noise' in draws else torch.rand((b, n), device=device)
+        perm_noise = draws['perm_noise'].to(device) if 'perm_noise' in draws else torch.rand((b, n), device=device, generator=generator)
         perm = perm_noise.argsort(dim=-1) - (n - num_tokens)[:, None]
         perm = perm.masked_fill(perm < 0, n)
         mask_token_mask = perm < num_masked[:, None]
         masked_input = torch.where(mask_token_mask, self.mask_id, ids)
+        return ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input
+
+    @torch.no_grad()
+    def objective_value(self, videos=None, *, texts=None, video_codebook_ids=None, video_frame_mask=None, text_embeds=None,
+                        cond_drop_prob=None, only_train_generator=False, only_train_critic=False, _draws=None):
+        """phenaki_pytorch.py:562-687 -- the VALUE of the training objective (masked-token cross entropy + weighted
+        token-critic BCE).  Forward only: the result carries no autograd graph (the backward kernels are SURVEY.md 8f
+        "next").  The 65 536-way logits are never written: pk_vocab_sample draws the critic's input ids and leaves the
+        softmax statistics, pk_vocab_ce turns them into per-row losses.  As in the reference, `cond_drop_prob` has no
+        effect on this path (it is shadowed by `cond_drop_prob = 0` at :594).
+        _draws (tests): dict(rand_step (b,), perm_noise (b,n) U[0,1), gumbel_u (b,n,V) U[0,1)) replaces the three
+        random draws of the reference (:620, :626 -> :43-55, :653)."""
+        assert not (only_train_generator and only_train_critic)
+        assert not (only_train_critic and not exists(self.critic)), 'only_train_critic needs a critic (Phenaki(critic=...) or self_token_critic=True)'
+        mg, critic = self.maskgit, self.critic
+        draws = _draws or {}
+        ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input = self._masked_batch(
+            videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws)
+        b, n = ids.shape
+        device = ids.device
 
         dt = compute_dtype_of(mg)
         D, V = mg.dim, mg.to_logits.weight.shape[0]
@@ -486,6 +501,63 @@ class Phenaki(PackedModule):
         if only_train_critic:
             return critic_loss
         return loss + critic_loss * self.critic_loss_weight
+
+    @torch.no_grad()
+    def evaluate(self, videos=None, *, texts=None, video_codebook_ids=None, video_frame_mask=None, text_embeds=None, mask_prob=None,
+                 generator=None, _draws=None):
+        """held-out evaluation of the masked-token model: the per-token numbers a MaskGIT-style model is judged by, on the masked positions of
+        one batch, without the (rows, V) logits (pk_vocab_eval).  Masking is that of the training objective (`objective_value`: the cosine
+        schedule over `steps`, then get_mask_subset_with_prob, phenaki_pytorch.py:620-628).
+        generator: a torch.Generator on the ids' device; the two draws (schedule step, permutation noise) come from it, so a validation set is
+            masked identically every time.
+        mask_prob: a number in (0, 1] replaces the schedule by that fixed fraction of every sample's tokens (1.0 masks them all).
+        _draws (tests): dict(rand_step (b,), perm_noise (b, n)) as in objective_value.
+        Returns a dict of device tensors; the host waits for nothing but the NUMBER of masked positions (the nonzero() that lists them, as in
+        objective_value).  With M masked positions in all:
+            rows (M,) int32 flat b * n + i of the masked positions, nll / entropy / lse (M,) f32 in nats, rank (M,) int32 = number of other
+            tokens the model scores above the true one (top-k accuracy is rank < k), pred (M,) int64 arg-max, mask (b, n) bool.
+        With a critic two more: critic_logits (b, n) = the critic's scores of the ids with the ARG-MAX pred filled in at the masked positions,
+        and critic_labels (b, n) bool = ids != filled.  The fill is deterministic: unlike the training objective (:653), which draws a gumbel
+        sample at critic_train_sample_temperature, a validation number must not move with a noise draw.
+        Runs in eval mode and under no_grad; every module's train / eval flag is left as found (eval_decorator's pattern, per module: a
+        Phenaki in train mode keeps its critic and tokenizer in eval mode)."""
+        flags = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            return self._evaluate(videos, texts, video_codebook_ids, video_frame_mask, text_embeds, mask_prob, generator, _draws)
+        finally:
+            for m, was_training in flags:
+                m.training = was_training
+
+    def _evaluate(self, videos, texts, video_codebook_ids, video_frame_mask, text_embeds, mask_prob, generator, _draws):
+        if exists(mask_prob) and not 0. < float(mask_prob) <= 1.:
+            raise ValueError(f'evaluate: mask_prob must be in (0, 1], got {mask_prob}')
+        mg, critic = self.maskgit, self.critic
+        ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input = self._masked_batch(
+            videos, texts, video_codebook_ids, video_frame_mask, text_embeds, _draws or {}, mask_prob, generator)
+        b, n = ids.shape
+        device = ids.device
+
+        dt = compute_dtype_of(mg)
+        D, V = mg.dim, mg.to_logits.weight.shape[0]
+        e = mg.embeds(masked_input, video_patch_shape=patch_shape, context=text_embeds, text_mask=text_mask, video_mask=video_mask)
+        rows = mask_token_mask.reshape(-1).nonzero().reshape(-1).int()      # >= 1 per sample (clamp(min=1) above)
+        M = rows.numel()
+        mixed = torch.empty((M, D), device=device, dtype=L.tdtype(dt))
+        L.cfg_mix(e, b, n, 0, rows, M, 1.0, False, mixed, D)                 # gather the masked rows, cast to T
+        f32 = lambda: torch.empty((M,), device=device, dtype=torch.float32)
+        out = dict(rows=rows, nll=f32(), entropy=f32(), lse=f32(), rank=torch.empty((M,), device=device, dtype=torch.int32),
+                   pred=torch.empty((M,), device=device, dtype=torch.long), mask=mask_token_mask)
+        L.vocab_eval(dt, mixed, linear_weight(mg.to_logits, dt), mg.to_logits.bias, M, V, D, ids.reshape(-1), rows,
+                     pred=out['pred'], lse=out['lse'], nll=out['nll'], rank=out['rank'], entropy=out['entropy'])
+        if exists(critic):
+            filled = ids.reshape(-1).clone()
+            filled[rows.long()] = out['pred']
+            filled = filled.view(b, n)
+            crit = critic(filled.view(b, *patch_shape), video_mask=video_mask, cond_drop_prob=0., text_mask=text_mask, context=text_embeds)
+            out['critic_logits'] = crit.reshape(b, n)
+            out['critic_labels'] = ids != filled
+        return out
 
     # ------------------------------------------------------------------------------------------ sampling (phenaki_pytorch.py:418-560)
 
