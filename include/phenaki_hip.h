@@ -630,6 +630,18 @@ int pk_frame_ssim(const float* a, const float* b, int B, int C, int F, int H, in
                   long long nparts, float* ssim, void* stream);
 int pk_code_usage(const int* counts, int V, double* out, void* stream);
 
+/* Cache policy of the result stores and read-once loads of the encode kernels (csrc/common.hpp).  The mask holds two bits
+ * per site, site i at bits 2 i .. 2 i + 1: policy 0 = plain, 1 = write-through (sc1) stores, 2 = non-temporal stores / loads.  Sites:
+ * 0 pk_gemm vector epilogue stores, 1 pk_qkv_attn O, 2 pk_peg (row kernel) outputs, 3 pk_layernorm / pk_layernorm_lfq outputs,
+ * 4 pk_patch_embed_splitk partials + statistics, 5 pk_patch_embed_finish outputs; loads (0 or 2 only): 6 the video lines of
+ * pk_patch_embed_splitk, 7 the partials of pk_patch_embed_finish, 8 the residual tile of pk_gemm.  Only cache bits change: results are
+ * bit-identical under every mask.  The process default is the environment's PK_CACHE_POLICY (unset or invalid: 0x2000, non-temporal video loads, the measured
+ * choice); the mask is read
+ * on the host at every launch, so a captured graph keeps the value it was captured with.  pk_set_cache_policy: PK_EINVAL for an
+ * unknown site or policy; pk_get_cache_policy returns the mask. */
+int pk_set_cache_policy(unsigned mask);
+int pk_get_cache_policy();
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,11 +146,14 @@ SIGNATURES = {
     'pk_frame_sqerr': [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P, _P],
     'pk_frame_ssim': [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _LL, _P, _P],
     'pk_code_usage': [_P, _I, _P, _P],
+    'pk_set_cache_policy': [ctypes.c_uint],
+    'pk_get_cache_policy': [],
 }
 
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
 
 _lib = None
+_AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy')
 
 
 def load():
@@ -162,6 +165,8 @@ def load():
                                '(the MI355X build has no CPU / eager fallback)')
         lib = ctypes.CDLL(LIB_PATH)
         for name, args in SIGNATURES.items():
+            if name in _AB_OPTIONAL and 'PK_LIB_PATH' in os.environ and not hasattr(lib, name):
+                continue                                   # an older build loaded for A/B timing: it has no policy switch (set / get then raise)
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = _I
@@ -238,6 +243,30 @@ def split_planes(w32):
 
 
 # ----------------------------------------------------------------------------- wrappers
+
+# cache-policy sites (include/phenaki_hip.h): two bits each, site i at bits 2 i .. 2 i + 1; stores 0 | 1 | 2, loads 0 | 2
+CP_PLAIN, CP_WT, CP_NT = 0, 1, 2
+CP_STORE_SITES = ('gemm', 'qkv_attn', 'peg', 'ln', 'patch_wide', 'patch_finish')
+CP_LOAD_SITES = ('ld_video', 'ld_partials', 'ld_residual')
+CP_SITES = CP_STORE_SITES + CP_LOAD_SITES
+
+
+def cache_policy_mask(**sites):
+    """mask of pk_set_cache_policy from site=policy pairs, e.g. cache_policy_mask(peg=CP_WT, ld_video=CP_NT)"""
+    mask = 0
+    for name, pol in sites.items():
+        mask |= int(pol) << (2 * CP_SITES.index(name))
+    return mask
+
+
+def set_cache_policy(mask):
+    """cache policy of the launches that follow (a captured graph keeps the one it was captured with)"""
+    _check(load().pk_set_cache_policy(int(mask)), 'pk_set_cache_policy')
+
+
+def get_cache_policy():
+    return load().pk_get_cache_policy()
+
 
 def gemm(dtype, A, W, M, N, K, *, C, bias=None, res=None, act=ACT_NONE, a_rows=None, lda=None, ldc=None, variant=0, C2=None, ln=None,
          scatter=None, stats_out=None, ln_stats=None, dup_rows=0):

@@ -179,6 +179,87 @@ __device__ __forceinline__ void store4(bf16* p, f32x4 v) {
 __device__ __forceinline__ void store2(float* p, float a, float b) { *reinterpret_cast<f32x2*>(p) = f32x2{a, b}; }
 __device__ __forceinline__ void store2(bf16* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = pack_bf2(a, b); }
 
+// ---- cache policy of result stores and read-once loads (DESIGN.md 4.1 "cache policy", knob PK_CACHE_POLICY) ---------------
+// A policy is a wave-uniform kernel argument and changes only the cache bits of the instruction: same address, same bytes, same order.
+//   CP_PLAIN  the ordinary store / load (the instruction the kernels always had)
+//   CP_WT     write-through store (sc1): the line goes to memory as it is written instead of staying dirty in L2 until the end-of-kernel
+//             write-back.  16-byte pieces go through a buffer descriptor of the output array (raw_buffer_store, aux 16 = sc1; 32-bit byte
+//             offsets: the host falls back to CP_PLAIN for an array that does not fit them), 4- and 8-byte pieces as relaxed agent-scope
+//             atomic stores (global_store ... sc1).  All are builtins, so the compiler counts them for vmcnt.
+//   CP_NT     non-temporal store / load (__builtin_nontemporal_*): streamed data that nothing in this launch touches again
+enum { CP_PLAIN = 0, CP_WT = 1, CP_NT = 2 };
+// the sites: two bits each in the mask, site i at bits 2 i .. 2 i + 1 (stores 0 | 1 | 2, loads 0 | 2)
+enum {
+    CPS_GEMM = 0,          // gemm_epilogue: C, C2, GEGLU pairs, stats_out pairs, scatter form
+    CPS_QKV_ATTN = 1,      // qkv_attn_kernel: O
+    CPS_PEG = 2,           // peg_row_kernel: both outputs
+    CPS_LN = 3,            // ln_rows_kernel / ln_lfq_kernel outputs
+    CPS_PATCH_WIDE = 4,    // patch_embed_wide_kernel: partials + statistics
+    CPS_PATCH_FINISH = 5,  // patch finish outputs
+    CPS_LD_VIDEO = 6,      // load: the wide patch kernel's video lines
+    CPS_LD_PART = 7,       // load: the finish kernel's partials
+    CPS_LD_RES = 8,        // load: the residual tile of gemm_epilogue
+    CPS_COUNT = 9
+};
+unsigned cache_policy_mask();                                     // host: the process-wide mask (elementwise.hip: pk_set_cache_policy)
+inline int cache_policy(int site) { return (int)((cache_policy_mask() >> (2 * site)) & 3u); }
+// the policy of a store site for an output array spanning `bytes`: write-through needs 32-bit byte offsets
+inline int cache_policy_for(int site, size_t bytes) {
+    const int pol = cache_policy(site);
+    return (pol == CP_WT && bytes >= 0xFFFFFFF0ull) ? CP_PLAIN : pol;
+}
+
+// A kernel takes its policy as an argument but keeps its plain form free of the choice: the store section is written once, as a generic
+// lambda over a compile-time flag, and entered through ONE wave-uniform branch --
+//     auto emit = [&](auto polc) { const int pol = cp_pick(polc, arg_pol); ... store4(pol_out(base, pol), base, o, v) ... };
+//     if (arg_pol) emit(CpOn{}); else emit(CpOff{});
+// so with CpOff the policy is the constant CP_PLAIN and the section compiles to the stores it always was.
+struct CpOn { static constexpr bool on = true; };
+struct CpOff { static constexpr bool on = false; };
+template <typename C> __device__ __forceinline__ int cp_pick(C, int pol) { return C::on ? pol : (int)CP_PLAIN; }
+
+typedef uint32_t u32x4_gcc __attribute__((__vector_size__(16)));
+// one output array and its policy; built once per kernel from the array's base
+struct PolOut { __amdgpu_buffer_rsrc_t rs; int pol; };
+__device__ __forceinline__ PolOut pol_out(void* base, int pol) {
+    return PolOut{__builtin_amdgcn_make_buffer_rsrc(base, 0, (int)0xFFFFFFFFu, 0x00020000), pol};
+}
+// 16 / 8 / 4 bytes to base + byte offset boff
+__device__ __forceinline__ void pol_store16(const PolOut& po, void* base, size_t boff, u32x4 v) {
+    if (po.pol == CP_WT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_gcc, v), po.rs, (int)(uint32_t)boff, 0, 16);
+    else if (po.pol == CP_NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(reinterpret_cast<char*>(base) + boff));
+    else *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(base) + boff) = v;
+}
+__device__ __forceinline__ void pol_store8(int pol, void* p, u32x2 v) {
+    if (pol == CP_WT) __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if (pol == CP_NT) __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(p));
+    else *reinterpret_cast<u32x2*>(p) = v;
+}
+__device__ __forceinline__ void pol_store4(int pol, void* p, uint32_t v) {
+    if (pol == CP_WT) __hip_atomic_store(reinterpret_cast<uint32_t*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if (pol == CP_NT) __builtin_nontemporal_store(v, reinterpret_cast<uint32_t*>(p));
+    else *reinterpret_cast<uint32_t*>(p) = v;
+}
+// store4 / store2 of element o of the array at `base`, by the array's policy (CP_PLAIN: exactly store4(base + o, v) / store2(base + o, a, b))
+__device__ __forceinline__ void store4(const PolOut& po, float* base, size_t o, f32x4 v) { pol_store16(po, base, o * 4, __builtin_bit_cast(u32x4, v)); }
+__device__ __forceinline__ void store4(const PolOut& po, bf16x3* base, size_t o, f32x4 v) { pol_store16(po, base, o * 4, __builtin_bit_cast(u32x4, v)); }
+// (pieces of 8 and 4 bytes need no descriptor: these forms also take the bare policy)
+__device__ __forceinline__ void store4(int pol, bf16* base, size_t o, f32x4 v) {
+    pol_store8(pol, base + o, u32x2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])});
+}
+__device__ __forceinline__ void store2(int pol, float* base, size_t o, float a, float b) {
+    pol_store8(pol, base + o, u32x2{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b)});
+}
+__device__ __forceinline__ void store2(int pol, bf16x3* base, size_t o, float a, float b) { store2(pol, reinterpret_cast<float*>(base), o, a, b); }
+__device__ __forceinline__ void store2(int pol, bf16* base, size_t o, float a, float b) { pol_store4(pol, base + o, pack_bf2(a, b)); }
+__device__ __forceinline__ void store4(const PolOut& po, bf16* base, size_t o, f32x4 v) { store4(po.pol, base, o, v); }
+template <typename T> __device__ __forceinline__ void store2(const PolOut& po, T* base, size_t o, float a, float b) { store2(po.pol, base, o, a, b); }
+// 16-byte load of a read-once stream
+__device__ __forceinline__ f32x4 pol_load16(int pol, const float* p) {
+    if (pol == CP_NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+    return *reinterpret_cast<const f32x4*>(p);
+}
+
 // ---- XCD-contiguous workgroup order -------------------------------------------------------
 // Workgroup b of a launch is observed to run on XCD b % 8, each XCD with a private 4 MB L2 (speed only, never
 // correctness).  A kernel whose NEIGHBOURING workgroups share data (the PEG stencil rows) launches 8 * per workgroups and

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void peg_kernel(const float* __restrict__ x, c
 template <int WW>
 __global__ __launch_bounds__(256) void peg_row_kernel(const float* __restrict__ x, const float* __restrict__ wt,
                                                       const float* __restrict__ bias, float* __restrict__ out, bf16* __restrict__ out_t,
-                                                      int B, int T, int H, int D, int tfront, long total, int flip = 0) {
+                                                      int B, int T, int H, int D, int tfront, long total, int flip = 0, int pol = CP_PLAIN) {
     const int dv = D >> 2;
     // XCD-contiguous order (common.hpp): a stencil row's 9 neighbour rows then sit in the SAME XCD's L2 -- 19.2 -> 13.3 us
     // at (16,9,8,8,512), bit-identical output (tools/peg_bench.hip)
@@ -91,12 +91,16 @@ __global__ __launch_bounds__(256) void peg_row_kernel(const float* __restrict__ 
         }
     }
     const size_t o0 = (((size_t)b * T + t) * H + h) * WW * D + c;
+    auto emit = [&](auto polc) {                             // both outputs by the site's policy (CPS_PEG; common.hpp)
+        const PolOut po = pol_out(out, cp_pick(polc, pol));
 #pragma unroll
-    for (int w = 0; w < WW; ++w) *reinterpret_cast<f32x4*>(out + o0 + (size_t)w * D) = acc[w];
-    if (out_t) {                                             // bf16 copy: the next GEMM's LDS-DMA operand
+        for (int w = 0; w < WW; ++w) store4(po, out, o0 + (size_t)w * D, acc[w]);
+        if (out_t) {                                         // bf16 copy: the next GEMM's LDS-DMA operand
 #pragma unroll
-        for (int w = 0; w < WW; ++w) store4(out_t + o0 + (size_t)w * D, acc[w]);
-    }
+            for (int w = 0; w < WW; ++w) store4(po, out_t, o0 + (size_t)w * D, acc[w]);
+        }
+    };
+    if (pol) emit(CpOn{}); else emit(CpOff{});
 }
 
 // (round 5: an LDS-staged form -- one sequence x one 16-channel slice per workgroup, the T*H*W x 64 B slab loaded once, every thread walking the time
@@ -308,8 +312,37 @@ __global__ __launch_bounds__(256) void gated_gelu_tanh_kernel(const float* __res
     }
 }
 
+// ---- the cache-policy mask (common.hpp): PK_CACHE_POLICY is the default, pk_set_cache_policy replaces it for the launches that follow.
+// Built-in default: non-temporal video loads in the wide patch kernel, the one site that won its A/B on MI355X (-16 ... -54 us of the batch-8
+// encode step); every store site and the other two load sites measured at or behind their plain form and stay plain (profiles/cache_policy.txt).
+constexpr unsigned CACHE_POLICY_DEFAULT = (unsigned)CP_NT << (2 * CPS_LD_VIDEO);
+static bool cache_policy_ok(unsigned mask) {
+    if (mask >> (2 * CPS_COUNT)) return false;
+    for (int s = 0; s < CPS_COUNT; ++s) {
+        const unsigned pol = (mask >> (2 * s)) & 3u;
+        if (pol == 3u || (s >= CPS_LD_VIDEO && pol == CP_WT)) return false;      // loads: plain or non-temporal
+    }
+    return true;
+}
+static unsigned& cache_policy_word() {
+    static unsigned mask = [] {
+        const char* e = getenv("PK_CACHE_POLICY");
+        const unsigned m = e ? (unsigned)strtoul(e, nullptr, 0) : CACHE_POLICY_DEFAULT;
+        return cache_policy_ok(m) ? m : CACHE_POLICY_DEFAULT;
+    }();
+    return mask;
+}
+unsigned cache_policy_mask() { return cache_policy_word(); }
+
 }  // namespace pk
 using namespace pk;
+
+extern "C" int pk_set_cache_policy(unsigned mask) {
+    if (!cache_policy_ok(mask)) return PK_EINVAL;
+    cache_policy_word() = mask;
+    return PK_OK;
+}
+extern "C" int pk_get_cache_policy() { return (int)cache_policy_word(); }
 
 static inline int nblocks(long total) { long b = (total + 255) / 256; return (int)(b < 16384 ? (b > 0 ? b : 1) : 16384); }
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
@@ -324,9 +357,10 @@ extern "C" int pk_peg(const float* x, const float* wt, const float* bias, float*
     const dim3 rgrid(xcd_padded_grid((rows + 255) / 256));
     bf16* ot = reinterpret_cast<bf16*>(out_t);
     if (ot && (reinterpret_cast<uintptr_t>(ot) & 7)) return PK_EALIGN;
-    if (W == 8) hipLaunchKernelGGL((peg_row_kernel<8>), rgrid, dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, D, causal ? 2 : 1, rows);
-    else if (W == 4) hipLaunchKernelGGL((peg_row_kernel<4>), rgrid, dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, D, causal ? 2 : 1, rows);
-    else if (W == 16) hipLaunchKernelGGL((peg_row_kernel<16>), rgrid, dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, D, causal ? 2 : 1, rows);
+    const int pol = cache_policy_for(CPS_PEG, (size_t)total * 16);
+    if (W == 8) hipLaunchKernelGGL((peg_row_kernel<8>), rgrid, dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, D, causal ? 2 : 1, rows, 0, pol);
+    else if (W == 4) hipLaunchKernelGGL((peg_row_kernel<4>), rgrid, dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, D, causal ? 2 : 1, rows, 0, pol);
+    else if (W == 16) hipLaunchKernelGGL((peg_row_kernel<16>), rgrid, dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, D, causal ? 2 : 1, rows, 0, pol);
     else hipLaunchKernelGGL(peg_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), x, wt, bias, out, ot, B, T, H, W, D, causal ? 2 : 1, total);
     PK_CHECK_LAUNCH();
     return PK_OK;

@@ -38,6 +38,9 @@ struct GemmEpilogue {
     // guidance batch are identical until the first cross-attention, so the first self-attention block runs on half the sequences and
     // its to_out GEMM writes both copies of the residual stream.
     int dup_rows;
+    // cache policies (common.hpp) of the vector epilogue: pol = every result store (C, C2, GEGLU pairs, stats_out pairs, scatter form; site CPS_GEMM),
+    // pol_res = the residual tile load (site CPS_LD_RES).  The scalar epilogue stays plain.
+    int pol, pol_res;
 };
 
 constexpr int STATS_CHUNK = 32;      // columns per partial: the 16 * TN columns one wave owns in every TN = 2 kernel
@@ -87,18 +90,18 @@ __device__ __forceinline__ void gemm_epilogue_scalar(const f32x4 (&acc)[TM][TN],
 // rows blocks (of 16 rows) per load round of the epilogue: IB * TN residual vectors in flight per lane
 template <int TM> constexpr int epi_rows_per_round() { return TM > 2 ? 2 : TM; }
 
-template <typename T, int TM, int TN, int WN = 2, bool LNF = false>
-__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M, int N, const GemmEpilogue& e, int m0, int n0,
-                                              const float* rsum = nullptr, const float* rsq = nullptr, int K = 1) {
-    if (!e.vec_ok) {
-        if (!LNF) gemm_epilogue_scalar<T, TM, TN, WN>(acc, M, N, e, m0, n0);
-        return;
-    }
+// POLC = CpOff: e.pol / e.pol_res are not read, every access is the plain one (the form every default launch runs)
+template <typename T, int TM, int TN, int WN, bool LNF, typename POLC>
+__device__ __forceinline__ void gemm_epilogue_vec(const f32x4 (&acc)[TM][TN], int M, int N, const GemmEpilogue& e, int m0, int n0,
+                                                  const float* rsum, const float* rsq, int K) {
+    const int e_pol = cp_pick(POLC{}, e.pol), e_pol_res = cp_pick(POLC{}, e.pol_res);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / WN, wn = wave % WN, g = lane >> 4, lr = lane & 15;
     float* __restrict__ Cf = reinterpret_cast<float*>(e.C);
     T* __restrict__ Ct = reinterpret_cast<T*>(e.C);
     const int mb = m0 + wm * 16 * TM + lr, nb = n0 + wn * 16 * TN + g * 4;      // + i*16, + j*16
+    const PolOut po = pol_out(e.C, e_pol);
+    bf16* const C2 = reinterpret_cast<bf16*>(e.C2);
     // N % 4 == 0 and N >= 4 here, so N - 4 is a valid clamped column; values loaded through a clamped index are never stored
     f32x4 b4[TN], s4[TN], t4[TN];
     int coff[TN];
@@ -124,7 +127,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M,
             roff[ii] = e.row_off ? e.row_off[mi] : 0;
             if (!LNF && e.res && e.act != ACT_GEGLU) {      // (a folded GEMM with a residual -- no such call on the hot path -- loads it in phase 2)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) r4[ii][j] = *reinterpret_cast<const f32x4*>(e.res + (size_t)mi * e.ldr + min(nb + j * 16, N - 4));
+                for (int j = 0; j < TN; ++j) r4[ii][j] = pol_load16(e_pol_res, e.res + (size_t)mi * e.ldr + min(nb + j * 16, N - 4));
             } else {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) r4[ii][j] = f32x4{0, 0, 0, 0};
@@ -154,7 +157,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M,
                 if (e.act == ACT_GEGLU) {
                     const float o0 = gelu_for<T>(v[1]) * v[0], o1 = gelu_for<T>(v[3]) * v[2];
                     const size_t o = (size_t)m * e.ldc + (n >> 1);
-                    if (live) { if (e.out_f32) store2(Cf + o, o0, o1); else store2(Ct + o, o0, o1); }
+                    if (live) { if (e.out_f32) store2(po, Cf, o, o0, o1); else store2(po, Ct, o, o0, o1); }
                     continue;
                 }
                 if (e.act == ACT_LEAKY) {
@@ -166,15 +169,18 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M,
                     for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
                 }
                 if (!LNF) v += r4[ii][j];
-                else if (e.res && live) v += *reinterpret_cast<const f32x4*>(e.res + (size_t)m * e.ldr + n);
+                else if (e.res && live) v += pol_load16(e_pol_res, e.res + (size_t)m * e.ldr + n);
                 if (live) {
                     const size_t o = e.row_off ? (size_t)((long)roff[ii] + (long)coff[j]) : (size_t)m * e.ldc + n;
-                    if (e.out_f32) store4(Cf + o, v); else store4(Ct + o, v);
-                    if (e.C2) store4(reinterpret_cast<bf16*>(e.C2) + (size_t)m * e.ldc2 + n, v);
+                    // (scatter form: the host does not know the span of the maps, so an element past the 32-bit byte offsets of the
+                    // write-through descriptor is stored plain)
+                    if (POLC::on && e.row_off && o >= ((size_t)1 << 30)) store4(Cf + o, v);
+                    else if (e.out_f32) store4(po, Cf, o, v); else store4(po, Ct, o, v);
+                    if (e.C2) store4(e_pol, C2, (size_t)m * e.ldc2 + n, v);
                     if (e.dup_rows) {
                         const size_t od = o + (size_t)e.dup_rows * e.ldc;
-                        if (e.out_f32) store4(Cf + od, v); else store4(Ct + od, v);
-                        if (e.C2) store4(reinterpret_cast<bf16*>(e.C2) + (size_t)(m + e.dup_rows) * e.ldc2 + n, v);
+                        if (e.out_f32) store4(po, Cf, od, v); else store4(po, Ct, od, v);
+                        if (e.C2) store4(e_pol, C2, (size_t)(m + e.dup_rows) * e.ldc2 + n, v);
                     }
                     if (TN == 2 && e.stats_out) {
 #pragma unroll
@@ -190,10 +196,21 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M,
                 ps += __shfl_xor(ps, 32); pq += __shfl_xor(pq, 32);
                 const int chunk = (n0 + wn * 16 * TN) / STATS_CHUNK;
                 if (g == 0 && m < M && chunk < e.stats_np)
-                    reinterpret_cast<float2*>(e.stats_out)[(size_t)m * e.stats_np + chunk] = float2{ps, pq};
+                    store2(e_pol, e.stats_out, ((size_t)m * e.stats_np + chunk) * 2, ps, pq);
             }
         }
     }
+}
+
+template <typename T, int TM, int TN, int WN = 2, bool LNF = false>
+__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M, int N, const GemmEpilogue& e, int m0, int n0,
+                                              const float* rsum = nullptr, const float* rsq = nullptr, int K = 1) {
+    if (!e.vec_ok) {
+        if (!LNF) gemm_epilogue_scalar<T, TM, TN, WN>(acc, M, N, e, m0, n0);
+        return;
+    }
+    if (e.pol | e.pol_res) gemm_epilogue_vec<T, TM, TN, WN, LNF, CpOn>(acc, M, N, e, m0, n0, rsum, rsq, K);      // wave-uniform
+    else gemm_epilogue_vec<T, TM, TN, WN, LNF, CpOff>(acc, M, N, e, m0, n0, rsum, rsq, K);
 }
 
 template <typename T, typename TA, int TM, int TN>
@@ -285,7 +302,9 @@ void gemm_dma_kernel(const GemmOperands p, const GemmEpilogue e, int a_nrows) {
         if (!Tile::run(p, a_nrows, m0, n0, smem, acc)) return;      // producer waves hold no accumulators
         PK_TL_KERNEL(1);
         gemm_epilogue<T, TM, TN, WN>(acc, p.M, p.N, e, m0, n0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef PK_TIMELINE
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stamp below is taken after the stores have been acknowledged
+#endif
         PK_TL_KERNEL(2);
     }
 }
@@ -513,6 +532,9 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
     bool v = (N % 4 == 0) && (ldc % 4 == 0) && al16(C) && (!bias || al16(bias)) && (!res || (al16(res) && ldr % 4 == 0));
     if (act == ACT_GEGLU) v = v && (ldc % 2 == 0) && ((reinterpret_cast<uintptr_t>(C) & 7) == 0);
     e.vec_ok = v ? 1 : 0;
+    // write-through stores address C through 32-bit byte offsets (the scatter form checks per element: gemm_epilogue)
+    e.pol = cache_policy_for(CPS_GEMM, row_off ? 0 : ((size_t)(M - 1 + dup_rows) * ldc + N) * (size_t)(out_is_f32 || dtype != 1 ? 4 : 2));
+    e.pol_res = cache_policy(CPS_LD_RES);
     if (C2 && (!v || !out_is_f32 || act == ACT_GEGLU || dtype != 1 || (ldc2 & 3) || (reinterpret_cast<uintptr_t>(C2) & 7))) return PK_EINVAL;
     if ((ln_s == nullptr) != (ln_t == nullptr)) return PK_EINVAL;
     if ((row_off == nullptr) != (col_off == nullptr)) return PK_EINVAL;

@@ -14,6 +14,7 @@ struct LnArgs {
     int M, D;
     int grp, gstride, goff;        // output row remap r -> (r / grp) * gstride + goff + r % grp        (grp > 0)
     int pb, pc;                    // output row remap (a, b, c) -> (a, c, b) over dims (M/(pb*pc), pb, pc) (pb > 0)
+    int pol;                       // cache policy of the output stores (common.hpp, site CPS_LN)
 };
 
 // one wave per row, D % 4 == 0, D <= 64*4*VMAX
@@ -63,24 +64,29 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const LnArgs p) {
         }
     }
     const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)p.D + p.eps);
+    auto emit = [&](auto polc) {                             // normalise and store by the site's policy (CPS_LN; common.hpp)
+        const int pol = cp_pick(polc, p.pol);
+        const PolOut po = pol_out(p.out, pol), po2 = pol_out(p.out2, pol), por = pol_out(p.raw, pol);
 #pragma unroll
-    for (int i = 0; i < VMAX; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            f32x4 g4, b4;
-            if constexpr (HOIST) { g4 = gm[i]; b4 = bt[i]; }
-            else {
-                g4 = *reinterpret_cast<const f32x4*>(p.gamma + c * 4);
-                b4 = p.beta ? *reinterpret_cast<const f32x4*>(p.beta + c * 4) : f32x4{0, 0, 0, 0};
+        for (int i = 0; i < VMAX; ++i) {
+            const int c = lane + i * 64;
+            if (c < nv) {
+                f32x4 g4, b4;
+                if constexpr (HOIST) { g4 = gm[i]; b4 = bt[i]; }
+                else {
+                    g4 = *reinterpret_cast<const f32x4*>(p.gamma + c * 4);
+                    b4 = p.beta ? *reinterpret_cast<const f32x4*>(p.beta + c * 4) : f32x4{0, 0, 0, 0};
+                }
+                f32x4 y;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) y[r] = (v[i][r] - mean) * rstd * g4[r] + b4[r];
+                if (out) store4(po, out, (size_t)orow * p.ldo + c * 4, y);
+                if (p.out2) store4(po2, p.out2, (size_t)orow * p.ldo2 + c * 4, y);
+                if (raw) store4(por, raw, (size_t)orow * p.ldraw + c * 4, v[i]);
             }
-            f32x4 y;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) y[r] = (v[i][r] - mean) * rstd * g4[r] + b4[r];
-            if (out) store4(out + (size_t)orow * p.ldo + c * 4, y);
-            if (p.out2) store4(p.out2 + (size_t)orow * p.ldo2 + c * 4, y);
-            if (raw) store4(raw + (size_t)orow * p.ldraw + c * 4, v[i]);
         }
-    }
+    };
+    if (p.pol) emit(CpOn{}); else emit(CpOff{});
 }
 
 // Final LayerNorm of the C-ViViT encoder fused with the lookup-free quantizer (cvivit.py:472 norm_out -> :570 LFQ): one wave
@@ -99,6 +105,7 @@ __global__ __launch_bounds__(256) void ln_lfq_kernel(const LnArgs p, const float
     const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
     if (row0 >= p.M) return;
     const int nv = p.D >> 2;
+    const PolOut po2 = pol_out(p.out2, p.pol);
     f32x4 y[R][VMAX];
     float mean[R], rstd[R];
 #pragma unroll
@@ -171,7 +178,7 @@ __global__ __launch_bounds__(256) void ln_lfq_kernel(const LnArgs p, const float
         if (p.out2) {
 #pragma unroll
             for (int i = 0; i < VMAX; ++i)
-                if (lane + i * 64 < nv) store4(p.out2 + (size_t)orow * p.ldo2 + (lane + i * 64) * 4, y[r][i]);
+                if (lane + i * 64 < nv) store4(po2, p.out2, (size_t)orow * p.ldo2 + (lane + i * 64) * 4, y[r][i]);
         }
         // halving butterfly: after the step with lane bit `bit`, a lane keeps the partials whose index has that bit equal to its own
         float h8[8], h4[4], h2[2], h1;
@@ -208,12 +215,12 @@ __global__ __launch_bounds__(256) void ln_lfq_kernel(const LnArgs p, const float
         h1 += __shfl_xor(h1, 1, 64);
         const int k = lane >> 2;                                 // bits 5..2 of the lane = bits 3..0 of k
         const float val = h1 + (k < cd ? bp[k] : 0.f);
-        if (proj && k < cd && (lane & 3) == 0) proj[(size_t)orow * cd + k] = val;
+        if (proj && k < cd && (lane & 3) == 0) pol_store4(p.pol, proj + (size_t)orow * cd + k, __builtin_bit_cast(uint32_t, val));
         const unsigned long long bal = __ballot(val > 0.f);
         if (lane == 0) {
             long long id = 0;
             for (int kk = 0; kk < cd; ++kk) id |= (long long)((bal >> (4 * kk)) & 1ull) << (cd - 1 - kk);
-            ids[orow] = id;
+            pol_store8(p.pol, ids + orow, __builtin_bit_cast(u32x2, id));
         }
     }
 }
@@ -299,7 +306,8 @@ extern "C" int pk_layernorm_lfq(const float* x, int ldx, const float* gamma, con
     if ((D & 3) || (ldx & 3) || (tokens && (ldt & 3))) return PK_EALIGN;
     if (D > 64 * 4 * 8) return PK_EINVAL;
     if (pb > 0 && (pc <= 0 || M % (pb * pc))) return PK_EINVAL;
-    LnArgs p{x, ldx, gamma, beta, eps, nullptr, 0, tokens, ldt, nullptr, 0, M, D, 0, 0, 0, pb, pc};
+    LnArgs p{x, ldx, gamma, beta, eps, nullptr, 0, tokens, ldt, nullptr, 0, M, D, 0, 0, 0, pb, pc,
+             cache_policy_for(CPS_LN, tokens ? (size_t)M * ldt * 4 : 0)};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 block(256);
     // rows per wave: 1 measured 10.4 us, 4 measured 14.1 us at 4608 x 512 (fewer, longer waves lose more than the 4x fewer
@@ -323,7 +331,11 @@ extern "C" int pk_layernorm(const float* x, int ldx, const float* gamma, const f
     if (D > 64 * 4 * 8) return PK_EINVAL;
     if (pb > 0 && (pc <= 0 || M % (pb * pc))) return PK_EINVAL;
     if (grp > 0 && pb > 0) return PK_EINVAL;
-    LnArgs p{x, ldx, gamma, beta, eps, out, ldo, out2, ldo2, raw, ldraw, M, D, grp, gstride, goff, pb, pc};
+    const size_t orows = grp > 0 ? (size_t)((M - 1) / grp) * gstride + goff + grp : (size_t)M;      // bound of the remapped output rows
+    size_t ldmax = out ? ldo : 0;
+    if (out2 && (size_t)ldo2 > ldmax) ldmax = ldo2;
+    if (raw && (size_t)ldraw > ldmax) ldmax = ldraw;
+    LnArgs p{x, ldx, gamma, beta, eps, out, ldo, out2, ldo2, raw, ldraw, M, D, grp, gstride, goff, pb, pc, cache_policy_for(CPS_LN, orows * ldmax * 4)};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 grid((M + 3) / 4), block(256);
     const bool small = D <= 64 * 4 * 2;

@@ -72,6 +72,10 @@ typedef __attribute__((address_space(3))) void* pe_lds_ptr;
 __device__ __forceinline__ void pe_load16(f32x4& dst, uint32_t voff, const u32x4& rsrc, uint32_t soff) {
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
+// the same load with the non-temporal bit (cache policy site CPS_LD_VIDEO: the video is read exactly once)
+__device__ __forceinline__ void pe_load16_nt(f32x4& dst, uint32_t voff, const u32x4& rsrc, uint32_t soff) {
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen nt" : "=v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
 template <int N>
 __device__ __forceinline__ void pe_wait(f32x4 (&r)[4]) {
     asm volatile("s_waitcnt vmcnt(%[cnt])" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : [cnt] "n"(N) : "memory");
@@ -337,9 +341,12 @@ struct PatchWideArgs {
     uint32_t video_bytes;
     int ngroups;
     int dbg;                  // diagnostics (PK_PATCH_DBG; results are WRONG when set): 1 = no MFMAs, 2 = no W stream, 4 = no A conversion
+    int pol;                  // cache policy of the partial / statistics stores (common.hpp, site CPS_PATCH_WIDE)
     PatchWideGroup g[2];
 };
 
+// NTV: the video loads carry the non-temporal bit (site CPS_LD_VIDEO); a compile-time choice, the loads sit in the counted pipeline
+template <bool NTV>
 __device__ __forceinline__ void patch_embed_wide_body(const PatchWideArgs& a, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -410,8 +417,13 @@ __device__ __forceinline__ void patch_embed_wide_body(const PatchWideArgs& a, ch
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const uint32_t so = next_soff();
-            pe_load16(r[half * 2 + 0], rowoff[0], rsrc, so);
-            pe_load16(r[half * 2 + 1], rowoff[1], rsrc, so);
+            if constexpr (NTV) {
+                pe_load16_nt(r[half * 2 + 0], rowoff[0], rsrc, so);
+                pe_load16_nt(r[half * 2 + 1], rowoff[1], rsrc, so);
+            } else {
+                pe_load16(r[half * 2 + 0], rowoff[0], rsrc, so);
+                pe_load16(r[half * 2 + 1], rowoff[1], rsrc, so);
+            }
         }
     };
 
@@ -521,26 +533,35 @@ __device__ __forceinline__ void patch_embed_wide_body(const PatchWideArgs& a, ch
 #pragma unroll
         for (int off = 1; off < 8; off <<= 1) { s += __shfl_xor(s, off, 64); q += __shfl_xor(q, off, 64); }
         const int m = m0 + wave * 16 + hrow * 8 + rr;
-        if (p == 0 && m < G.rows) reinterpret_cast<float2*>(G.stats)[(size_t)slice * G.rows + m] = float2{s, q};
+        if (p == 0 && m < G.rows) store2(a.pol, G.stats, ((size_t)slice * G.rows + m) * 2, s, q);
     }
     // ---- raw partial product: lane holds 4 consecutive columns of rows wm*64 + i*16 + lr
     float* part = G.part + (size_t)slice * G.rows * a.N;
+    auto emit = [&](auto polc) {                            // by the site's policy (CPS_PATCH_WIDE; common.hpp)
+        const PolOut po = pol_out(part, cp_pick(polc, a.pol));      // one slice of one group: rows * N * 4 bytes (host: fits 32-bit offsets or plain)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + wm * 64 + i * 16 + lr;
-        if (m >= G.rows) continue;
+        for (int i = 0; i < 4; ++i) {
+            const int m = m0 + wm * 64 + i * 16 + lr;
+            if (m >= G.rows) continue;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int n = wn * 128 + j * 16 + g * 4;
-            if (n < a.N) store4(part + (size_t)m * a.N + n, acc[i][j]);
+            for (int j = 0; j < 8; ++j) {
+                const int n = wn * 128 + j * 16 + g * 4;
+                if (n < a.N) store4(po, part, (size_t)m * a.N + n, acc[i][j]);
+            }
         }
-    }
+    };
+    if (a.pol) emit(CpOn{}); else emit(CpOff{});
 }
 
 __global__ __launch_bounds__(64 * PE_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))       // the whole LDS: one workgroup per CU
 void patch_embed_wide_kernel(const PatchWideArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    patch_embed_wide_body(a, smem);
+    patch_embed_wide_body<false>(a, smem);
+}
+__global__ __launch_bounds__(64 * PE_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void patch_embed_wide_nt_kernel(const PatchWideArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    patch_embed_wide_body<true>(a, smem);
 }
 
 // pk_patch_embed_finish: one wave per token row.  y = rstd (sum_s part_s - mean' s) + t over the row's P features (statistics = the slices'
@@ -551,6 +572,7 @@ struct PatchFinishArgs {
     const float* gamma2; const float* beta2; float eps2;
     float* out2; bf16* out; int ldo2, ldo;
     int remap_in, remap_out, remap_off;
+    int pol_st, pol_ld;       // cache policies (common.hpp): the output stores (site CPS_PATCH_FINISH), the partial loads (site CPS_LD_PART)
 };
 __device__ __forceinline__ void patch_embed_finish_rows(const PatchFinishArgs& a, int block) {
     const int lane = threadIdx.x & 63;
@@ -573,7 +595,7 @@ __device__ __forceinline__ void patch_embed_finish_rows(const PatchFinishArgs& a
         y[q] = f32x4{0, 0, 0, 0};
         if (n < a.N) {
             f32x4 acc = f32x4{0, 0, 0, 0};
-            for (int sl = 0; sl < a.nslices; ++sl) acc += *reinterpret_cast<const f32x4*>(a.part + ((size_t)sl * a.rows + row) * a.N + n);
+            for (int sl = 0; sl < a.nslices; ++sl) acc += pol_load16(a.pol_ld, a.part + ((size_t)sl * a.rows + row) * a.N + n);
             const f32x4 s4 = *reinterpret_cast<const f32x4*>(a.s + n), t4 = *reinterpret_cast<const f32x4*>(a.t + n);
 #pragma unroll
             for (int r = 0; r < 4; ++r) { y[q][r] = rstd * (acc[r] - mean * s4[r]) + t4[r]; ls += y[q][r]; }
@@ -588,6 +610,7 @@ __device__ __forceinline__ void patch_embed_finish_rows(const PatchFinishArgs& a
             for (int r = 0; r < 4; ++r) { const float d = y[q][r] - m2; lq = fmaf(d, d, lq); }
     const float r2 = 1.0f / sqrtf(wave_sum(lq) / (float)a.N + a.eps2);
     const int orow = a.remap_in > 0 ? (row / a.remap_in) * a.remap_out + a.remap_off + row % a.remap_in : row;
+    const PolOut po2 = pol_out(a.out2, a.pol_st);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int n = lane * 4 + q * 256;
@@ -596,8 +619,8 @@ __device__ __forceinline__ void patch_embed_finish_rows(const PatchFinishArgs& a
         f32x4 v;
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = (y[q][r] - m2) * r2 * g4[r] + b4[r];
-        if (a.out2) store4(a.out2 + (size_t)orow * a.ldo2 + n, v);
-        if (a.out) store4(a.out + (size_t)orow * a.ldo + n, v);
+        if (a.out2) store4(po2, a.out2, (size_t)orow * a.ldo2 + n, v);
+        if (a.out) store4(a.pol_st, a.out, (size_t)orow * a.ldo + n, v);      // (8-byte pieces: no descriptor)
     }
 }
 __global__ __launch_bounds__(256) void patch_embed_finish_kernel(const PatchFinishArgs a) { patch_embed_finish_rows(a, blockIdx.x); }
@@ -684,6 +707,7 @@ extern "C" int pk_patch_embed_splitk(const float* video, int B, int C, int F, in
     a.N = N; a.video_bytes = (uint32_t)vbytes; a.ngroups = ngroups;
     static const int dbg_env = [] { const char* e = getenv("PK_PATCH_DBG"); return e ? atoi(e) : 0; }();      // timing decomposition only
     a.dbg = dbg_env;
+    a.pol = cache_policy(CPS_PATCH_WIDE);
     const void* Ws[2] = {W0, W1}; const int ldws[2] = {ldw0, ldw1}; float* parts[2] = {part0, part1}; float* stt[2] = {stats0, stats1};
     const int f0s[2] = {f00, f01}, nts[2] = {nt0, nt1}, pts[2] = {pt0, pt1};
     int work = 0;
@@ -698,12 +722,18 @@ extern "C" int pk_patch_embed_splitk(const float* video, int B, int C, int F, in
         G.rows = B * nts[gi] * a.nh * a.nw;
         G.mtiles = (G.rows + PE_BM - 1) / PE_BM;
         G.nslices = (G.K + PW_KS - 1) / PW_KS;
+        if ((size_t)G.rows * N * 4 >= 0xFFFFFFF0ull && a.pol == CP_WT) a.pol = CP_PLAIN;      // a slice's partial rows: 32-bit byte offsets
         work += G.mtiles * G.nslices;
     }
     if (ngroups == 1) a.g[1] = a.g[0];
-    static pk::LdsOptIn lds;
-    if (lds.raise(reinterpret_cast<const void*>(&patch_embed_wide_kernel), PW_SMEM) != PK_OK) return PK_ELAUNCH;
-    hipLaunchKernelGGL(patch_embed_wide_kernel, dim3(8 * ((work + 7) / 8)), dim3(64 * PE_WAVES), PW_SMEM, reinterpret_cast<hipStream_t>(stream), a);
+    static pk::LdsOptIn lds, lds_nt;
+    if (cache_policy(CPS_LD_VIDEO) == CP_NT) {
+        if (lds_nt.raise(reinterpret_cast<const void*>(&patch_embed_wide_nt_kernel), PW_SMEM) != PK_OK) return PK_ELAUNCH;
+        hipLaunchKernelGGL(patch_embed_wide_nt_kernel, dim3(8 * ((work + 7) / 8)), dim3(64 * PE_WAVES), PW_SMEM, reinterpret_cast<hipStream_t>(stream), a);
+    } else {
+        if (lds.raise(reinterpret_cast<const void*>(&patch_embed_wide_kernel), PW_SMEM) != PK_OK) return PK_ELAUNCH;
+        hipLaunchKernelGGL(patch_embed_wide_kernel, dim3(8 * ((work + 7) / 8)), dim3(64 * PE_WAVES), PW_SMEM, reinterpret_cast<hipStream_t>(stream), a);
+    }
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
@@ -718,7 +748,9 @@ extern "C" int pk_patch_embed_finish(const float* part, const float* stats, int 
     if (mis(part) || mis(s) || mis(t) || mis(gamma2) || mis(beta2) || (out2 && (mis(out2) || (ldo2 & 3))) || (out && ((reinterpret_cast<uintptr_t>(out) & 7) || (ldo & 3))) ||
         (reinterpret_cast<uintptr_t>(stats) & 7)) return PK_EALIGN;
     if (remap_in < 0 || (remap_in > 0 && (remap_out < remap_in || remap_off < 0))) return PK_EINVAL;
-    PatchFinishArgs a{part, stats, nslices, rows, N, K, s, t, eps1, gamma2, beta2, eps2, out2, reinterpret_cast<bf16*>(out), ldo2, ldo, remap_in, remap_out, remap_off};
+    const size_t orows = remap_in > 0 ? (size_t)((rows - 1) / remap_in) * remap_out + remap_off + remap_in : (size_t)rows;      // bound of the remapped output rows
+    PatchFinishArgs a{part, stats, nslices, rows, N, K, s, t, eps1, gamma2, beta2, eps2, out2, reinterpret_cast<bf16*>(out), ldo2, ldo, remap_in, remap_out, remap_off,
+                      cache_policy_for(CPS_PATCH_FINISH, out2 ? orows * ldo2 * 4 : 0), cache_policy(CPS_LD_PART)};
     hipLaunchKernelGGL(patch_embed_finish_kernel, dim3((rows + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     PK_CHECK_LAUNCH();
     return PK_OK;
@@ -736,7 +768,9 @@ extern "C" int pk_patch_embed_finish_groups(const pk_patch_finish_group* g, int 
         if (mis(d.part) || mis(d.s) || mis(d.t) || mis(d.gamma2) || mis(d.beta2) || (reinterpret_cast<uintptr_t>(d.stats) & 7)) return PK_EALIGN;
         if (d.remap_in < 0 || (d.remap_in > 0 && (d.remap_out < d.remap_in || d.remap_off < 0))) return PK_EINVAL;
         p.g[i] = PatchFinishArgs{d.part, d.stats, d.nslices, d.rows, N, d.K, d.s, d.t, d.eps1, d.gamma2, d.beta2, d.eps2, out2, reinterpret_cast<bf16*>(out), ldo2, ldo,
-                                 d.remap_in, d.remap_out, d.remap_off};
+                                 d.remap_in, d.remap_out, d.remap_off,
+                                 cache_policy_for(CPS_PATCH_FINISH, out2 ? ((d.remap_in > 0 ? (size_t)((d.rows - 1) / d.remap_in) * d.remap_out + d.remap_off + d.remap_in : (size_t)d.rows) * ldo2 * 4) : 0),
+                                 cache_policy(CPS_LD_PART)};
     }
     if (ngroups == 1) p.g[1] = p.g[0];
     p.blocks0 = (p.g[0].rows + 3) / 4;

@@ -29,6 +29,7 @@ struct QkvAttnArgs {
     void* O; int ldo;                       // bf16 [(s*n + i)][hh*64 + d]
     uint32_t recip;                         // ceil(65536 / n): x / n == (x * recip) >> 16 for x < 64
     const float* q_ln_s;                    // LayerNorm folded into to_q (see pk_qkv_project): xq = the un-normalised rows, wq = gamma (.) Wq
+    int pol;                                // cache policy of the O store (common.hpp, site CPS_QKV_ATTN)
 };
 
 template <typename T> using QaTile = GemmDma<T, 1, 4, 4, 1, 2, 128>;          // 64 rows x 64 columns (one head), 4 waves stacked on the rows
@@ -262,9 +263,13 @@ __global__ __launch_bounds__(256) void qkv_attn_kernel(const QkvAttnArgs a) {
     }
     if (!qvalid) return;
     const float inv = 1.0f / ls;
-    T* orow = reinterpret_cast<T*>(a.O) + (size_t)(m0 + rq) * a.ldo + hh * 64;
+    const size_t orow = (size_t)(m0 + rq) * a.ldo + hh * 64;
+    auto emit = [&](auto polc) {                             // the O store by the site's policy (CPS_QKV_ATTN; common.hpp)
+        const PolOut po = pol_out(a.O, cp_pick(polc, a.pol));
 #pragma unroll
-    for (int df = 0; df < 4; ++df) store4(orow + df * 16 + g * 4, o[df] * inv);
+        for (int df = 0; df < 4; ++df) store4(po, reinterpret_cast<T*>(a.O), orow + df * 16 + g * 4, o[df] * inv);
+    };
+    if (a.pol) emit(CpOn{}); else emit(CpOff{});
 }
 
 // ---- cross-attention against CACHED keys / values (the step-invariant text context of MaskGit / TokenCritic, attention.py:142-182
@@ -438,6 +443,7 @@ extern "C" int pk_qkv_attn(int dtype, const void* xq, const void* xkv, int ld, c
     a.O = O; a.ldo = ldo;
     a.recip = (65536u + (uint32_t)n - 1u) / (uint32_t)n;
     a.q_ln_s = q_ln_s;
+    a.pol = cache_policy_for(CPS_QKV_ATTN, (size_t)M * ldo * esz);
     if (q_ln_s && mis(q_ln_s)) return PK_EALIGN;
     const int tiles = (S + a.spt - 1) / a.spt;
     dim3 grid(8 * ((tiles + 7) / 8) * h);
