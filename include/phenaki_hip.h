@@ -642,6 +642,27 @@ int pk_code_usage(const int* counts, int V, double* out, void* stream);
 int pk_set_cache_policy(unsigned mask);
 int pk_get_cache_policy();
 
+/* Compile-time epilogue forms of pk_gemm_ex (csrc/gemm.hip).  The three GEMM calls of a bf16 transformer block -- Attention
+ * to_out, FeedForward first and second Linear -- run an epilogue in which every option is a compile-time constant, with one copy for
+ * tiles inside the matrix (no bounds predicates) and one for edge tiles; results are bit-identical to the generic epilogue.  Forms:
+ * 0 generic; 1 OUT (variant 8: f32 residual, f32 C, bf16 C2, stats_out); 2 FF2A (variant 8: f32 residual, f32 C, bf16 C2); 3 FF2B (the same
+ * without C2); 4 FF1 (variant 24, LayerNorm fold with ln_stats: GEGLU, bf16 C).  All: dtype 1, vector epilogue, no bias, no scatter, no
+ * dup_rows, both gemm cache policies plain.
+ *   pk_gemm_epilogue_form: pure; the form of a launch from the fields it sees (variant: the resolved main loop; ln_kind 0 no fold, 1
+ *                          in-loop statistics, 2 ln_stats; pol / pol_res: the policies of sites 0 and 8).
+ *   pk_gemm_ex_form:       pk_gemm_ex's arguments without the stream -> the form that call would launch now (>= 0), or its error (< 0);
+ *                          launches nothing, dereferences no pointer.
+ *   pk_set_gemm_hot_forms: 0 forces form 0 for the launches that follow (default 1, or the environment's PK_GEMM_HOT_FORMS); read on the
+ *                          host at every launch, so a captured graph keeps the form it was captured with. */
+int pk_gemm_epilogue_form(int dtype, int variant, int ln_kind, int vec_ok, int act, int out_is_f32, int has_bias, int has_res, int has_c2,
+                          int has_stats_out, int has_scatter, int dup_rows, int pol, int pol_res);
+int pk_gemm_ex_form(int dtype, int a_is_f32, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
+                    const float* res, int ldr, void* C, int ldc, int out_is_f32, int act, const int* a_rows, int a_nrows, int variant,
+                    void* C2, int ldc2, const float* ln_s, const float* ln_t, float ln_eps, const int* row_off, const int* col_off,
+                    float* stats_out, const float* ln_stats, int dup_rows);
+int pk_set_gemm_hot_forms(int on);
+int pk_get_gemm_hot_forms();
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,12 +148,16 @@ SIGNATURES = {
     'pk_code_usage': [_P, _I, _P, _P],
     'pk_set_cache_policy': [ctypes.c_uint],
     'pk_get_cache_policy': [],
+    'pk_gemm_epilogue_form': [_I] * 14,
+    'pk_gemm_ex_form': [_I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _I],
+    'pk_set_gemm_hot_forms': [_I],
+    'pk_get_gemm_hot_forms': [],
 }
 
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
 
 _lib = None
-_AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy')
+_AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy', 'pk_gemm_epilogue_form', 'pk_gemm_ex_form', 'pk_set_gemm_hot_forms', 'pk_get_gemm_hot_forms')
 
 
 def load():
@@ -268,6 +272,49 @@ def get_cache_policy():
     return load().pk_get_cache_policy()
 
 
+# epilogue forms of pk_gemm_ex (include/phenaki_hip.h)
+EPI_GENERIC, EPI_OUT, EPI_FF2A, EPI_FF2B, EPI_FF1 = 0, 1, 2, 3, 4
+
+
+def set_gemm_hot_forms(on):
+    """0: every GEMM launch that follows takes the generic epilogue (a captured graph keeps the form it was captured with)"""
+    _check(load().pk_set_gemm_hot_forms(1 if on else 0), 'pk_set_gemm_hot_forms')
+
+
+def get_gemm_hot_forms():
+    return load().pk_get_gemm_hot_forms()
+
+
+def gemm_epilogue_form(dtype, variant, *, ln_kind=0, vec_ok=1, act=ACT_NONE, out_is_f32=1, bias=0, res=0, C2=0, stats_out=0, scatter=0,
+                       dup_rows=0, pol=0, pol_res=0):
+    """pk_gemm_epilogue_form: the form of a launch from its fields (flags: whether the operand is passed)"""
+    return load().pk_gemm_epilogue_form(dtype, variant, ln_kind, int(vec_ok), act, int(out_is_f32), int(bool(bias)), int(bool(res)), int(bool(C2)),
+                                        int(bool(stats_out)), int(bool(scatter)), int(dup_rows), int(pol), int(pol_res))
+
+
+def _gemm_args(dtype, A, W, M, N, K, *, C, bias=None, res=None, act=ACT_NONE, a_rows=None, lda=None, ldc=None, variant=0, C2=None, ln=None,
+               scatter=None, stats_out=None, ln_stats=None, dup_rows=0):
+    """pk_gemm_ex's arguments up to (not including) the stream"""
+    a_is_f32 = 1 if A.dtype == torch.float32 else 0
+    out_is_f32 = 1 if C.dtype == torch.float32 else 0
+    lda = A.stride(-2) if lda is None else lda
+    ldc = (C.stride(-2) if scatter is None else N) if ldc is None else ldc
+    ldr = res.stride(-2) if res is not None else 0
+    return (dtype, a_is_f32, ptr(A), lda, ptr(W), W.stride(0), M, N, K, f32p(bias, 'bias'), f32p(res, 'residual'), ldr,
+            ptr(C), ldc, out_is_f32, act, ptr(a_rows), A.shape[0] if a_rows is not None else M, variant,
+            ptr(C2), C2.stride(-2) if C2 is not None else 0, ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None,
+            float(ln[2]) if ln else 0., ptr(scatter[0]) if scatter else None, ptr(scatter[1]) if scatter else None,
+            ptr(stats_out) if stats_out is not None else None, ptr(ln_stats) if ln_stats is not None else None, int(dup_rows))
+
+
+def gemm_form(dtype, A, W, M, N, K, **kw):
+    """the epilogue form (EPI_*) gemm() would launch for exactly these arguments now; launches nothing, reads no operand (any device)"""
+    rc = load().pk_gemm_ex_form(*_gemm_args(dtype, A, W, M, N, K, **kw))
+    if rc < 0:
+        _check(rc, 'pk_gemm_ex_form')
+    return rc
+
+
 def gemm(dtype, A, W, M, N, K, *, C, bias=None, res=None, act=ACT_NONE, a_rows=None, lda=None, ldc=None, variant=0, C2=None, ln=None,
          scatter=None, stats_out=None, ln_stats=None, dup_rows=0):
     """C = act(A @ W^T + bias) (+ res).  A: (rows, K) f32 or T; W: (N, Kpad) T; C preallocated.
@@ -277,16 +324,8 @@ def gemm(dtype, A, W, M, N, K, *, C, bias=None, res=None, act=ACT_NONE, a_rows=N
     written to C.view(-1)[row_off[m] + col_off[n]] (f32 C of any shape; the un-patchify map).  stats_out (M, ceil(N/32), 2) f32: per-chunk
     (sum, sum of squares) of every output row for the LayerNorm-folded GEMM that consumes it, which passes the same buffer as ln_stats.
     dup_rows: every output row m of C / C2 is also written at row m + dup_rows."""
-    a_is_f32 = 1 if A.dtype == torch.float32 else 0
-    out_is_f32 = 1 if C.dtype == torch.float32 else 0
-    lda = A.stride(-2) if lda is None else lda
-    ldc = (C.stride(-2) if scatter is None else N) if ldc is None else ldc
-    ldr = res.stride(-2) if res is not None else 0
-    rc = load().pk_gemm_ex(dtype, a_is_f32, ptr(A), lda, ptr(W), W.stride(0), M, N, K, f32p(bias, 'bias'), f32p(res, 'residual'), ldr,
-                           ptr(C), ldc, out_is_f32, act, ptr(a_rows), A.shape[0] if a_rows is not None else M, variant,
-                           ptr(C2), C2.stride(-2) if C2 is not None else 0, ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None,
-                           float(ln[2]) if ln else 0., ptr(scatter[0]) if scatter else None, ptr(scatter[1]) if scatter else None,
-                           ptr(stats_out) if stats_out is not None else None, ptr(ln_stats) if ln_stats is not None else None, int(dup_rows), stream(C))
+    rc = load().pk_gemm_ex(*_gemm_args(dtype, A, W, M, N, K, C=C, bias=bias, res=res, act=act, a_rows=a_rows, lda=lda, ldc=ldc, variant=variant, C2=C2,
+                                       ln=ln, scatter=scatter, stats_out=stats_out, ln_stats=ln_stats, dup_rows=dup_rows), stream(C))
     _check(rc, 'pk_gemm_ex')
     return C
 

@@ -90,10 +90,116 @@ __device__ __forceinline__ void gemm_epilogue_scalar(const f32x4 (&acc)[TM][TN],
 // rows blocks (of 16 rows) per load round of the epilogue: IB * TN residual vectors in flight per lane
 template <int TM> constexpr int epi_rows_per_round() { return TM > 2 ? 2 : TM; }
 
+// ---- compile-time epilogue forms (pk_gemm_epilogue_form picks one on the host) -------------------------------------------------
+// The generic vector epilogue below decides every option -- activation, residual, bias, output type, C2, dup_rows, scatter, stats_out --
+// with a wave-uniform run-time branch inside its unrolled TM x TN loops, although one call takes a single sparse path through them.
+// The three layer calls of a bf16 transformer block get that path as straight-line code instead: every option a constant, no bias (the
+// calls pass none: a constant 0, not loaded), no scatter, no dup_rows, plain cache policy.  Same loads, same stores (address, width,
+// order) and the same floating-point operations in the same order as the generic path, so results are bit-identical.
+//   EPI_OUT   64x64 tile (variant 8): f32 residual in, f32 C, bf16 C2, stats_out partials         (Attention to_out)
+//   EPI_FF2A  64x64 tile (variant 8): f32 residual in, f32 C, bf16 C2                              (FeedForward second Linear)
+//   EPI_FF2B  the same without C2
+//   EPI_FF1   128x128 8-wave tile (variant 24), LayerNorm fold with handed-over statistics: GEGLU, bf16 pair stores, no residual
+enum { EPI_GENERIC = 0, EPI_OUT = 1, EPI_FF2A = 2, EPI_FF2B = 3, EPI_FF1 = 4 };
+
+// EDGE = false: the whole tile lies inside the matrix, so no `live` predicate and no clamped address; EDGE = true keeps both
+template <int TM, int TN, int WN, int FORM, bool EDGE>
+__device__ __forceinline__ void gemm_epilogue_form(const f32x4 (&acc)[TM][TN], int M, int N, const GemmEpilogue& e, int m0, int n0,
+                                                   const float* rsum, const float* rsq, int K) {
+    constexpr bool FF1 = FORM == EPI_FF1, HAS_C2 = FORM == EPI_OUT || FORM == EPI_FF2A, STATS = FORM == EPI_OUT;
+    static_assert(TN == 2, "one 32-column statistics chunk per wave");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave / WN, wn = wave % WN, g = lane >> 4, lr = lane & 15;
+    float* __restrict__ Cf = reinterpret_cast<float*>(e.C);
+    bf16* __restrict__ Ct = reinterpret_cast<bf16*>(e.C);
+    bf16* const C2 = reinterpret_cast<bf16*>(e.C2);
+    const int mb = m0 + wm * 16 * TM + lr, nb = n0 + wn * 16 * TN + g * 4;      // + i*16, + j*16
+    const f32x4 b4 = f32x4{0, 0, 0, 0};                     // the null bias: still added (-0 + 0 = +0, as in the generic path)
+    f32x4 s4[TN], t4[TN];
+    if constexpr (FF1) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int nj = EDGE ? min(nb + j * 16, N - 4) : nb + j * 16;
+            s4[j] = *reinterpret_cast<const f32x4*>(e.ln_s + nj);
+            t4[j] = *reinterpret_cast<const f32x4*>(e.ln_t + nj);
+        }
+    }
+    constexpr int IB = TM > 2 ? 2 : TM;                     // epi_rows_per_round
+#pragma unroll
+    for (int i0 = 0; i0 < TM; i0 += IB) {
+        // ---- phase 1: loads
+        f32x4 r4[IB][TN];
+        if constexpr (!FF1) {
+#pragma unroll
+            for (int ii = 0; ii < IB; ++ii) {
+                const int mi = EDGE ? min(mb + (i0 + ii) * 16, M - 1) : mb + (i0 + ii) * 16;
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    r4[ii][j] = *reinterpret_cast<const f32x4*>(e.res + (size_t)mi * e.ldr + (EDGE ? min(nb + j * 16, N - 4) : nb + j * 16));
+            }
+        }
+        // ---- phase 2: math and stores
+#pragma unroll
+        for (int ii = 0; ii < IB; ++ii) {
+            const int i = i0 + ii, m = mb + i * 16;
+            float mean = 0.f, rstd = 1.f;
+            if constexpr (FF1) {
+                const float inv_k = 1.0f / (float)K;
+                mean = rsum[i] * inv_k;
+                rstd = __builtin_amdgcn_rsqf(fmaxf(rsq[i] * inv_k - mean * mean, 0.f) + e.ln_eps);
+            }
+            float ps = 0.f, pq = 0.f;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int n = nb + j * 16;
+                const bool live = !EDGE || (m < M && n < N);
+                f32x4 v = acc[i][j];
+                if constexpr (FF1) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = rstd * (v[r] - mean * s4[j][r]) + t4[j][r];
+                    v += b4;
+                    const float o0 = gelu_for<bf16>(v[1]) * v[0], o1 = gelu_for<bf16>(v[3]) * v[2];
+                    if (live) store2(Ct + ((size_t)m * e.ldc + (n >> 1)), o0, o1);
+                } else {
+                    v += b4;
+                    v += r4[ii][j];
+                    if (live) {
+                        store4(Cf + ((size_t)m * e.ldc + n), v);
+                        if constexpr (HAS_C2) store4(C2 + ((size_t)m * e.ldc2 + n), v);
+                        if constexpr (STATS) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float x = bf2f(f2bf(v[r]));      // as the consumer reads the C2 copy
+                                ps += x; pq += x * x;
+                            }
+                        }
+                    }
+                }
+            }
+            if constexpr (STATS) {
+                ps += __shfl_xor(ps, 16); pq += __shfl_xor(pq, 16);
+                ps += __shfl_xor(ps, 32); pq += __shfl_xor(pq, 32);
+                const int chunk = (n0 + wn * 16 * TN) / STATS_CHUNK;
+                if (g == 0 && (!EDGE || (m < M && chunk < e.stats_np)))
+                    store2(e.stats_out + ((size_t)m * e.stats_np + chunk) * 2, ps, pq);
+            }
+        }
+    }
+}
+
 // POLC = CpOff: e.pol / e.pol_res are not read, every access is the plain one (the form every default launch runs)
-template <typename T, int TM, int TN, int WN, bool LNF, typename POLC>
+// FORM != 0 (bf16, CpOff): one of the compile-time forms above, as two straight-line copies chosen by ONE wave-uniform test at entry
+template <typename T, int TM, int TN, int WN, bool LNF, typename POLC, int FORM = EPI_GENERIC>
 __device__ __forceinline__ void gemm_epilogue_vec(const f32x4 (&acc)[TM][TN], int M, int N, const GemmEpilogue& e, int m0, int n0,
                                                   const float* rsum, const float* rsq, int K) {
+    if constexpr (FORM != EPI_GENERIC) {
+        static_assert(sizeof(T) == 2 && !POLC::on && LNF == (FORM == EPI_FF1), "hot forms: bf16, plain cache policy");
+        static_assert(FORM == EPI_FF1 ? (TM == 4 && TN == 2 && WN == 4) : (TM == 2 && TN == 2 && WN == 2), "hot forms: the 64x64 / 8-wave 128x128 tiles");
+        constexpr int BM = 2 * 16 * TM, BN = WN * 16 * TN;  // (both tiles stack 2 waves along m)
+        if (m0 + BM <= M && n0 + BN <= N) gemm_epilogue_form<TM, TN, WN, FORM, false>(acc, M, N, e, m0, n0, rsum, rsq, K);
+        else gemm_epilogue_form<TM, TN, WN, FORM, true>(acc, M, N, e, m0, n0, rsum, rsq, K);
+        return;
+    }
     const int e_pol = cp_pick(POLC{}, e.pol), e_pol_res = cp_pick(POLC{}, e.pol_res);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / WN, wn = wave % WN, g = lane >> 4, lr = lane & 15;
@@ -202,9 +308,13 @@ __device__ __forceinline__ void gemm_epilogue_vec(const f32x4 (&acc)[TM][TN], in
     }
 }
 
-template <typename T, int TM, int TN, int WN = 2, bool LNF = false>
+template <typename T, int TM, int TN, int WN = 2, bool LNF = false, int FORM = EPI_GENERIC>
 __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M, int N, const GemmEpilogue& e, int m0, int n0,
                                               const float* rsum = nullptr, const float* rsq = nullptr, int K = 1) {
+    if constexpr (FORM != EPI_GENERIC) {                  // the host launches a form only with vec_ok and both policies plain
+        gemm_epilogue_vec<T, TM, TN, WN, LNF, CpOff, FORM>(acc, M, N, e, m0, n0, rsum, rsq, K);
+        return;
+    }
     if (!e.vec_ok) {
         if (!LNF) gemm_epilogue_scalar<T, TM, TN, WN>(acc, M, N, e, m0, n0);
         return;
@@ -235,7 +345,7 @@ constexpr int lds_waves_per_simd() {
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
 
-template <typename T, int TM, int TN, int WM, int WN, int STAGES, int ROWB, int PW, int LNF = 0>
+template <typename T, int TM, int TN, int WM, int WN, int STAGES, int ROWB, int PW, int LNF = 0, int FORM = EPI_GENERIC>
 __global__ __launch_bounds__(64 * (WM * WN + PW))
 __attribute__((amdgpu_waves_per_eu(lds_waves_per_simd<GemmDma<T, TM, TN, WM, WN, STAGES, ROWB, PW>>(), 8)))
 void gemm_dma_kernel(const GemmOperands p, const GemmEpilogue e, int a_nrows) {
@@ -297,11 +407,11 @@ void gemm_dma_kernel(const GemmOperands p, const GemmEpilogue e, int a_nrows) {
         const int lane = threadIdx.x & 63, wm = (threadIdx.x >> 6) / WN;
 #pragma unroll
         for (int i = 0; i < TM; ++i) { const float2 pr = ls[wm * 16 * TM + i * 16 + (lane & 15)]; rsum[i] = pr.x; rsq[i] = pr.y; }
-        gemm_epilogue<T, TM, TN, WN, true>(acc, p.M, p.N, e, m0, n0, rsum, rsq, p.K);
+        gemm_epilogue<T, TM, TN, WN, true, FORM>(acc, p.M, p.N, e, m0, n0, rsum, rsq, p.K);
     } else {
         if (!Tile::run(p, a_nrows, m0, n0, smem, acc)) return;      // producer waves hold no accumulators
         PK_TL_KERNEL(1);
-        gemm_epilogue<T, TM, TN, WN>(acc, p.M, p.N, e, m0, n0);
+        gemm_epilogue<T, TM, TN, WN, false, FORM>(acc, p.M, p.N, e, m0, n0);
 #ifdef PK_TIMELINE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stamp below is taken after the stores have been acknowledged
 #endif
@@ -355,19 +465,19 @@ static int launch_v1(const GemmOperands& p, const GemmEpilogue& e, hipStream_t s
     return PK_OK;
 }
 
-template <typename T, int TM, int TN, int STAGES, int WM = 2, int WN = 2, int ROWB = 128, int PW = 0, int LNF = 0>
+template <typename T, int TM, int TN, int STAGES, int WM = 2, int WN = 2, int ROWB = 128, int PW = 0, int LNF = 0, int FORM = EPI_GENERIC>
 static int launch_dma(const GemmOperands& p, const GemmEpilogue& e, int a_nrows, hipStream_t s) {
     using Tile = GemmDma<T, TM, TN, WM, WN, STAGES, ROWB, PW>;
     if (Tile::SMEM > 65536) {
         static LdsOptIn lds;
-        if (lds.raise(reinterpret_cast<const void*>(&gemm_dma_kernel<T, TM, TN, WM, WN, STAGES, ROWB, PW, LNF>), Tile::SMEM) != PK_OK) return PK_ELAUNCH;
+        if (lds.raise(reinterpret_cast<const void*>(&gemm_dma_kernel<T, TM, TN, WM, WN, STAGES, ROWB, PW, LNF, FORM>), Tile::SMEM) != PK_OK) return PK_ELAUNCH;
     }
     const int MT = (p.M + Tile::BM - 1) / Tile::BM, NT = (p.N + Tile::BN - 1) / Tile::BN;
     dim3 grid(8 * ((MT + 7) / 8) * NT);                   // see the XCD-aware tile map in the kernel
     GemmOperands pp = p;
     static const int panel_env = [] { const char* e_ = getenv("PK_GEMM_PANEL"); return e_ ? atoi(e_) : -1; }();      // tuning knob: 0 = off, n = m-tiles per panel
     pp.panel = panel_env >= 0 ? panel_env : xcd_panel_rows(Tile::BM, p.K, (int)sizeof(T));
-    hipLaunchKernelGGL((gemm_dma_kernel<T, TM, TN, WM, WN, STAGES, ROWB, PW, LNF>), grid, dim3(Tile::THREADS), Tile::SMEM, s, pp, e, a_nrows);
+    hipLaunchKernelGGL((gemm_dma_kernel<T, TM, TN, WM, WN, STAGES, ROWB, PW, LNF, FORM>), grid, dim3(Tile::THREADS), Tile::SMEM, s, pp, e, a_nrows);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
@@ -505,13 +615,38 @@ extern "C" int pk_gemm_auto_variant(int dtype, int a_is_f32, int M, int N, int K
     return auto_variant(dtype, a_is_f32, M, N, K, lda, ldw, a_nrows);
 }
 
+// ---- compile-time epilogue forms: the switch and the host-side choice
+// PK_GEMM_HOT_FORMS=0 / pk_set_gemm_hot_forms(0): every launch takes the generic epilogue (A/B of the two paths in one process)
+static int& hot_forms_word() {
+    static int on = [] { const char* e_ = getenv("PK_GEMM_HOT_FORMS"); return e_ ? (atoi(e_) != 0 ? 1 : 0) : 1; }();
+    return on;
+}
+extern "C" int pk_set_gemm_hot_forms(int on) { hot_forms_word() = on ? 1 : 0; return PK_OK; }
+extern "C" int pk_get_gemm_hot_forms() { return hot_forms_word(); }
+
+// the epilogue form (EPI_*) of a launch from the fields the launch itself sees: dtype and the resolved main-loop variant, ln_kind (0 no
+// LayerNorm fold, 1 in-loop statistics, 2 handed-over statistics), GemmEpilogue's vec_ok / act / out_f32 / pol / pol_res / dup_rows and
+// which of its optional operands are set.  A form only where the call IS that form; everything else 0, the generic epilogue.  Pure:
+// the process switch above is applied by pk_gemm_ex.
+extern "C" int pk_gemm_epilogue_form(int dtype, int variant, int ln_kind, int vec_ok, int act, int out_is_f32, int has_bias, int has_res,
+                                     int has_c2, int has_stats_out, int has_scatter, int dup_rows, int pol, int pol_res) {
+    if (dtype != 1 || !vec_ok || pol || pol_res || has_bias || has_scatter || dup_rows) return EPI_GENERIC;
+    if (variant == 8 && ln_kind == 0 && act == ACT_NONE && out_is_f32 && has_res) {
+        if (has_stats_out) return has_c2 ? EPI_OUT : EPI_GENERIC;
+        return has_c2 ? EPI_FF2A : EPI_FF2B;
+    }
+    if (variant == 24 && ln_kind == 2 && act == ACT_GEGLU && !out_is_f32 && !has_res && !has_c2 && !has_stats_out) return EPI_FF1;
+    return EPI_GENERIC;
+}
+
 // variant: 0 = automatic; 1/2 = register-staged 64x64 / 128x128; 8 = DMA 64x64 2 stages; 9 / 24 = DMA 128x128 (4 / 8 waves);
 //          27 = DMA 128x64 4 waves (bf16); 33 = DMA 64x64 with 2 producer waves, 3 stages (bf16); 3 = DMA 64x64 4 stages (f32)   (explicit: tools/gemm_bench.py)
-extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const void* W, int ldw,
-                          int M, int N, int K, const float* bias, const float* res, int ldr,
-                          void* C, int ldc, int out_is_f32, int act, const int* a_rows, int a_nrows,
-                          int variant, void* C2, int ldc2, const float* ln_s, const float* ln_t, float ln_eps,
-                          const int* row_off, const int* col_off, float* stats_out, const float* ln_stats, int dup_rows, void* stream) {
+// form_only: validate and dispatch as usual, but instead of launching report the epilogue form the launch would take
+static int gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const void* W, int ldw,
+                   int M, int N, int K, const float* bias, const float* res, int ldr,
+                   void* C, int ldc, int out_is_f32, int act, const int* a_rows, int a_nrows,
+                   int variant, void* C2, int ldc2, const float* ln_s, const float* ln_t, float ln_eps,
+                   const int* row_off, const int* col_off, float* stats_out, const float* ln_stats, int dup_rows, void* stream, int* form_only) {
     if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C) return PK_EINVAL;
     if (dtype != 0 && dtype != 1 && dtype != 2) return PK_EINVAL;
     if (act < 0 || act > 3) return PK_EINVAL;
@@ -548,9 +683,14 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
     if (variant >= 100) { p.plain_map = 1; variant -= 100; }
     if (variant == 0) variant = auto_variant(dtype, a_is_f32, M, N, K, lda, ldw, a_nrows);
     if (variant >= 3 && !dma_ok) return PK_EINVAL;
+    const int form = !hot_forms_word() ? EPI_GENERIC
+                   : pk_gemm_epilogue_form(dtype, variant, ln_s ? (ln_stats ? 2 : 1) : 0, e.vec_ok, act, out_is_f32, bias != nullptr, res != nullptr,
+                                           C2 != nullptr, stats_out != nullptr, row_off != nullptr, dup_rows, e.pol, e.pol_res);
     if (ln_s) {
         // LayerNorm-folded GEMM: LDS-DMA main loop only (the statistics come from its A fragments), vector epilogue, 64x64 / 128x128 tiles
         if (!dma_ok || !v || !al16(ln_s) || !al16(ln_t) || a_rows) return PK_EINVAL;
+        if (form_only) { *form_only = form; return PK_OK; }
+        if (form == EPI_FF1) return launch_dma<bf16, 4, 2, 2, 2, 4, 128, 0, 2, EPI_FF1>(p, e, a_nrows, s);
         // 128x128 wherever the automatic choice is a large tile (50: the 256x256 loop, which has no folded form)
         const bool big = variant == 24 || variant == 2 || variant == 9 || variant == 50;
         if (ln_stats) {
@@ -565,6 +705,10 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
     }
     // stats_out is written by the TN = 2 LDS-DMA kernels only (one 32-column chunk per wave)
     if (stats_out && !(dma_ok && (variant == 8 || variant == 24 || variant == 27 || variant == 33 || variant == 50 || (variant == 3 && dtype != 1)))) return PK_EINVAL;
+    if (form_only) { *form_only = form; return PK_OK; }
+    if (form == EPI_OUT) return launch_dma<bf16, 2, 2, 2, 2, 2, 128, 0, 0, EPI_OUT>(p, e, a_nrows, s);
+    if (form == EPI_FF2A) return launch_dma<bf16, 2, 2, 2, 2, 2, 128, 0, 0, EPI_FF2A>(p, e, a_nrows, s);
+    if (form == EPI_FF2B) return launch_dma<bf16, 2, 2, 2, 2, 2, 128, 0, 0, EPI_FF2B>(p, e, a_nrows, s);
     // the main-loop variants that survived round 1's sweep (profiles/gemm_variants*_r01.txt; the 35 losers -- deeper rings, k-tile 32,
     // 128x256 / 256x256 tiles, other wave layouts, other producer / consumer splits -- were deleted in round 2)
     if (dtype == 1) {
@@ -606,6 +750,28 @@ extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const
         case 24: return launch_dma<float, 4, 2, 2, 2, 4>(p, e, a_nrows, s);
         default: return PK_EINVAL;
     }
+}
+
+extern "C" int pk_gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const void* W, int ldw,
+                          int M, int N, int K, const float* bias, const float* res, int ldr,
+                          void* C, int ldc, int out_is_f32, int act, const int* a_rows, int a_nrows,
+                          int variant, void* C2, int ldc2, const float* ln_s, const float* ln_t, float ln_eps,
+                          const int* row_off, const int* col_off, float* stats_out, const float* ln_stats, int dup_rows, void* stream) {
+    return gemm_ex(dtype, a_is_f32, A, lda, W, ldw, M, N, K, bias, res, ldr, C, ldc, out_is_f32, act, a_rows, a_nrows, variant, C2, ldc2, ln_s, ln_t, ln_eps,
+                   row_off, col_off, stats_out, ln_stats, dup_rows, stream, nullptr);
+}
+
+// the epilogue form (>= 0) pk_gemm_ex would launch for exactly this call under the current cache-policy mask and hot-forms switch, or
+// pk_gemm_ex's error (< 0); nothing is launched and no pointer is dereferenced
+extern "C" int pk_gemm_ex_form(int dtype, int a_is_f32, const void* A, int lda, const void* W, int ldw,
+                               int M, int N, int K, const float* bias, const float* res, int ldr,
+                               void* C, int ldc, int out_is_f32, int act, const int* a_rows, int a_nrows,
+                               int variant, void* C2, int ldc2, const float* ln_s, const float* ln_t, float ln_eps,
+                               const int* row_off, const int* col_off, float* stats_out, const float* ln_stats, int dup_rows) {
+    int form = EPI_GENERIC;
+    const int rc = gemm_ex(dtype, a_is_f32, A, lda, W, ldw, M, N, K, bias, res, ldr, C, ldc, out_is_f32, act, a_rows, a_nrows, variant, C2, ldc2, ln_s, ln_t,
+                           ln_eps, row_off, col_off, stats_out, ln_stats, dup_rows, nullptr, &form);
+    return rc != PK_OK ? rc : form;
 }
 
 #ifdef PK_TIMELINE
