@@ -245,7 +245,7 @@ int pk_layernorm_lfq(const float* x, int ldx, const float* gamma, const float* b
                      int pb, int pc, void* stream);
 
 /* rows of x scaled to unit l2 norm (F.normalize, eps 1e-12), out in T (out_kind 1) or f32: the query side of the cosine-sim
- * VectorQuantize lookup (cvivit.py:321). */
+ * VectorQuantize lookup (cvivit.py:321).  x 16-byte aligned, out 16-byte (f32) / 8-byte (T) aligned, else PK_EALIGN. */
 int pk_l2norm_rows(const float* x, int ldx, void* out, int ldo, int out_kind, int M, int D, void* stream);
 
 /* phenaki_pytorch.py:194-197, 290-291 (+ the prime-token concat of :500): S sequences of n_tot = n_prime + n positions,

@@ -287,7 +287,8 @@ extern "C" int pk_rmsnorm(const float* x, int ldx, const float* w, float eps, co
 
 extern "C" int pk_l2norm_rows(const float* x, int ldx, void* out, int ldo, int out_kind, int M, int D, void* stream) {
     if (!x || !out || M <= 0 || D <= 0) return PK_EINVAL;
-    if ((D & 3) || (ldx & 3) || (ldo & 3)) return PK_EALIGN;
+    if ((D & 3) || (ldx & 3) || (ldo & 3) || (reinterpret_cast<uintptr_t>(x) & 15) ||
+        (reinterpret_cast<uintptr_t>(out) & (out_kind == 0 ? 15 : 7))) return PK_EALIGN;      // 16-byte row loads, 16- / 8-byte stores
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 grid((M + 3) / 4), block(256);
     if (out_kind == 0) hipLaunchKernelGGL((l2norm_rows_kernel<float>), grid, block, 0, s, x, ldx, (float*)out, ldo, M, D);
