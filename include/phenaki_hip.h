@@ -305,7 +305,8 @@ int pk_q_attn_cached(int dtype, const void* xq, int ld, const void* wq, int ldw,
  * bias[hh][i][j] is over the real (non-null) keys; kmask [S][n_kv] uint8 (1 = keep); slopes [h] with causal.
  * pk_attn_fwd_dh / pk_attn_fwd_lse_dh: the same on the images of pk_attn_prep_dh(dim_head, ...), dim_head = 32 | 64 | 128 (else PK_EINVAL).
  * 64 is pk_attn_fwd / pk_attn_fwd_lse.  32 and 128 always run on the LDS-free kernel: bias_tab, a finite score_bound or a dropout site
- * is PK_EINVAL there (the LDS-staged kernels, the fused projection kernels and the backward kernels are built for 64). */
+ * is PK_EINVAL there (the LDS-staged kernels, the fused projection kernels and the backward kernels are built for 64).
+ * dtype 0 and 2 write O as f32: out_is_f32 = 0 is PK_EINVAL with them. */
 int pk_attn_fwd(int dtype, const void* Qp, const void* Kp, const void* Vt, const float* bias, long bias_hstride,
                 int bias_ld, const unsigned char* kmask, const float* slopes, int causal, void* O, int ldo,
                 int out_is_f32, int S, int h, int nq, int n_kv, int nnull, const float* bias_tab, int tab_len,

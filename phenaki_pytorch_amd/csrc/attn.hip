@@ -986,6 +986,7 @@ static int attn_fwd_launch(int dtype, int QF, bool images_ok, dim3 grid, dim3 bl
         else if (QF == 2) attn_fwd_one<bf16, 2, DROP, DH>(grid, block, s, a, dr);
         else attn_fwd_one<bf16, 1, DROP, DH>(grid, block, s, a, dr);
     } else if (dtype == 0) {
+        if (!a.out_f32) return PK_EINVAL;                     // the f32 kernel stores O as T = float whatever out_is_f32 says: a bf16 O would be overrun
         if (QF == 2) attn_fwd_one<float, 2, DROP, DH>(grid, block, s, a, dr);
         else attn_fwd_one<float, 1, DROP, DH>(grid, block, s, a, dr);
     } else if (dtype == 2) {
