@@ -25,6 +25,9 @@ def main():
     ap.add_argument('--small', action='store_true', help='a small geometry (dim 128, 64 x 64 pixels) instead of the BASELINE one')
     ap.add_argument('--attn-dropout', type=float, default=0., help='dropout on the attention probabilities of MaskGit and the critic (in training mode)')
     ap.add_argument('--ff-dropout', type=float, default=0., help='dropout behind GEGLU in their feed-forwards')
+    ap.add_argument('--label-smoothing', type=float, default=0., help='label smoothing of the masked-token cross entropy, in [0, 1) (the MaskGIT recipe: 0.1)')
+    ap.add_argument('--z-loss', type=float, default=0., help='weight of the z-loss, mean logsumexp(logits)^2 (PaLM: 1e-4), against logit drift of the 65 536-way head')
+    ap.add_argument('--cond-drop', action='store_true', help='classifier-free-guidance dropout in the training step (Phenaki(train_cond_drop=True), cond_drop_prob 0.25)')
     ap.add_argument('--max-grad-norm', type=float, default=None, help='clip the global gradient norm inside the AdamW update (phenaki_trainer.py:380-381)')
     ap.add_argument('--eval-every', type=int, default=0, help='every N steps rank 0 runs --eval-batches held-out batches through MaskGitMetrics and prints one line')
     ap.add_argument('--eval-batches', type=int, default=2)
@@ -44,7 +47,8 @@ def main():
                         attn_dropout=args.attn_dropout, ff_dropout=args.ff_dropout)
     critic = P.TokenCritic(dim=dim, num_tokens=vocab, max_seq_len=1024, depth=2 if args.small else 6, heads=dim // 64, dim_head=64, dim_context=ctx_dim,
                            has_cross_attn=True, attn_dropout=args.attn_dropout, ff_dropout=args.ff_dropout)
-    phenaki = P.Phenaki(cvivit=cvivit, maskgit=maskgit, critic=critic, text_embed_dim=ctx_dim).cuda()
+    phenaki = P.Phenaki(cvivit=cvivit, maskgit=maskgit, critic=critic, text_embed_dim=ctx_dim, label_smoothing=args.label_smoothing, z_loss_weight=args.z_loss,
+                        train_cond_drop=args.cond_drop).cuda()
     P.set_compute_dtype(phenaki, args.dtype)
     params = list(maskgit.parameters()) + list(critic.parameters())
     opt = P.get_optimizer(params, lr=1e-4, wd=1e-2, max_grad_norm=args.max_grad_norm)

@@ -381,6 +381,23 @@ int pk_vocab_reduce(const void* partials, int M, int V, const int* rows, const u
  * target logit is the dot product of row m of A with row targets[r] of W (+ bias) -- same A / W / bias as that call. */
 int pk_vocab_ce(int dtype, const void* partials, int M, int V, const void* A, int lda, const void* W, int ldw,
                 const float* bias, int D, const long long* targets, const int* rows, float* loss, float* lse_out, void* stream);
+/* The regularised form of that loss: label smoothing eps = label_smoothing in [0, 1) (torch's F.cross_entropy(label_smoothing=): eps is spread
+ * over all V classes, the target included) and the PaLM z-loss with weight zeta = z_loss_weight >= 0,
+ *     loss[m] = lse_m - (1 - eps) logit[m][t_m] - eps zbar_m + zeta lse_m^2,     zbar_m = mean_v logit[m][v] = A[m] . wbar + bbar,
+ * one more D-long dot product per row.  wbar [D] f32 / bbar [1] f32: the means over the V rows of W and over the bias, left on the device by
+ * pk_vocab_weight_mean (the host never reads them); they may be NULL when label_smoothing == 0.  lse_out is the plain log-sum-exp.
+ * label_smoothing outside [0, 1), z_loss_weight < 0 or not finite, wbar / bbar == NULL with label_smoothing > 0: PK_EINVAL.
+ * pk_vocab_ce is the (0, 0, NULL, NULL) call: it launches the same kernel it always did. */
+int pk_vocab_ce_reg(int dtype, const void* partials, int M, int V, const void* A, int lda, const void* W, int ldw,
+                    const float* bias, int D, const long long* targets, const int* rows, float* loss, float* lse_out,
+                    float label_smoothing, float z_loss_weight, const float* wbar, const float* bbar, void* stream);
+/* wbar[c] = mean_v W[v][c] (c < D) and bbar[0] = mean_v bias[v] of a vocabulary head, from the operand image W [V][ldw] exactly as the head's
+ * main loop reads it (dtype 0 f32, 1 bf16, 2 the split-bf16 planes as hi + lo: ldw % 32 == 0).  One streaming pass, two launches, a fixed
+ * summation order without atomics: two calls agree bit for bit.  Only wbar[0, D) and bbar[0] are written.
+ * workspace: pk_vocab_weight_mean_words(dtype, V, D) 4-byte words.  D and ldw multiples of 4 (bf16: 8), W 16-byte aligned. */
+int pk_vocab_weight_mean_words(int dtype, int V, int D);
+int pk_vocab_weight_mean(int dtype, const void* W, int ldw, const float* bias, int V, int D, float* wbar, float* bbar, void* workspace,
+                         void* stream);
 /* The validation statistics of the vocab head (what a MaskGIT-style model is judged by: masked-token perplexity, top-k accuracy, the rank
  * of the true token, the entropy of the predictive distribution) in one pass over the vocabulary, again without the logits; same A / lda /
  * W / ldw / bias / M / V / D / rows as pk_vocab_sample, no noise, no temperature, no atomics.  pk_vocab_eval first forms the target logit
@@ -408,6 +425,13 @@ int pk_vocab_eval_reduce(const void* workspace, int M, int V, long long* pred, f
 int pk_ce_grad_slab(int out_bf16, const float* logits, int ldl, const float* lse, const long long* targets, const int* rows,
                     int M, int Vs, int v0, float scale, const float* scale_dev, void* g, int ldg, void* gT, int ldgt, float* db, void* stream);
 /* scale_dev (or NULL): a device scalar multiplied into scale -- the upstream gradient of the loss, read on the device */
+/* The gradient of the regularised loss (pk_vocab_ce_reg), same buffers:
+ *     g[m][v] = (exp(logit - lse[m]) (1 + 2 zeta lse[m]) - (1 - eps) [v0 + v == targets[r]] - eps / V_total) * scale,
+ * V_total the WHOLE vocabulary (v0 + Vs <= V_total), not the slab; dE, dW and db follow from g as before.  Argument errors as pk_vocab_ce_reg;
+ * pk_ce_grad_slab is the (0, 0, -) call and launches the same kernel it always did. */
+int pk_ce_grad_slab_reg(int out_bf16, const float* logits, int ldl, const float* lse, const long long* targets, const int* rows,
+                        int M, int Vs, int v0, float scale, const float* scale_dev, void* g, int ldg, void* gT, int ldgt, float* db,
+                        float label_smoothing, float z_loss_weight, int V_total, void* stream);
 
 /* phenaki_pytorch.py:488-491: mask = zeros.scatter(1, scores.topk(k).indices, 1).bool(); ids = where(mask, mask_id, ids).
  * rows_out (B*k int32, or NULL) receives the flat positions b*n + i of the masked tokens: only those rows need the vocab

@@ -81,10 +81,14 @@ SIGNATURES = {
     'pk_vocab_sample': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _ULL, _P, _I, _P, _P],
     'pk_vocab_reduce': [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     'pk_vocab_ce': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
+    'pk_vocab_ce_reg': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P],
+    'pk_vocab_weight_mean_words': [_I, _I, _I],
+    'pk_vocab_weight_mean': [_I, _P, _I, _P, _I, _I, _P, _P, _P, _P],
     'pk_vocab_eval_words': [_I],
     'pk_vocab_eval': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
     'pk_vocab_eval_reduce': [_P, _I, _I, _P, _P, _P, _P, _P, _P],
     'pk_ce_grad_slab': [_I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P],
+    'pk_ce_grad_slab_reg': [_I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _F, _F, _I, _P],
     'pk_topk_mask': [_P, _I, _I, _I, _LL, _P, _P, _P, _P, _P],
     'pk_critic_head': [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _F, _ULL, _P, _P, _P],
     'pk_pack': [_P, _LL, _P, _I, _I, _I, _P, _LL, _I, _I, _P],
@@ -157,7 +161,8 @@ SIGNATURES = {
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
 
 _lib = None
-_AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy', 'pk_gemm_epilogue_form', 'pk_gemm_ex_form', 'pk_set_gemm_hot_forms', 'pk_get_gemm_hot_forms')
+_AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy', 'pk_gemm_epilogue_form', 'pk_gemm_ex_form', 'pk_set_gemm_hot_forms', 'pk_get_gemm_hot_forms',
+                'pk_vocab_ce_reg', 'pk_ce_grad_slab_reg', 'pk_vocab_weight_mean', 'pk_vocab_weight_mean_words')
 
 
 def load():
@@ -773,11 +778,64 @@ def vocab_reduce(partials, M, V, rows, mask, ids, pred, scores, need_lse):
     _check(rc, 'pk_vocab_reduce')
 
 
-def vocab_ce(dtype, partials, M, V, A, W, bias, D, targets, rows, loss, lse=None):
-    """loss[m] = lse(logits[m]) - logits[m][targets[rows[m]]] from the partials of vocab_sample(..., need_lse=True); lse (M,) f32 optional"""
-    rc = load().pk_vocab_ce(dtype, ptr(partials), M, V, ptr(A), A.stride(-2), ptr(W), W.stride(0), f32p(bias, 'to_logits.bias'), D,
-                            ptr(targets), ptr(rows), ptr(loss), ptr(lse), stream(A))
-    _check(rc, 'pk_vocab_ce')
+def check_ce_regularisers(label_smoothing, z_loss_weight, who='vocab_cross_entropy'):
+    """(label_smoothing, z_loss_weight) as floats; ValueError unless 0 <= label_smoothing < 1 and 0 <= z_loss_weight < inf (NaN fails both)"""
+    try:
+        eps, zeta = float(label_smoothing), float(z_loss_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: label_smoothing and z_loss_weight must be numbers, got {label_smoothing!r} and {z_loss_weight!r}') from None
+    if not (0. <= eps < 1.):
+        raise ValueError(f'{who}: label_smoothing must be in [0, 1), got {label_smoothing!r}')
+    if not (0. <= zeta < float('inf')):
+        raise ValueError(f'{who}: z_loss_weight must be finite and >= 0, got {z_loss_weight!r}')
+    return eps, zeta
+
+
+def vocab_weight_mean(dtype, Wimg, bias, V, D, wbar=None, bbar=None, workspace=None):
+    """(wbar (D,) f32, bbar (1,) f32): the means over the V rows of the head's operand image Wimg -- read as the main loop reads it (f32, bf16,
+    or the split-bf16 planes as hi + lo) -- and over bias, on the device (pk_vocab_weight_mean; fixed summation order, no host read).
+    wbar / bbar: buffers to write into (only wbar[:D] and bbar[0] are written), else allocated here."""
+    if dtype not in (F32, BF16, BF16X3):
+        raise ValueError(f'vocab_weight_mean: unknown compute dtype {dtype}')
+    require_device(Wimg, 'W image')
+    if Wimg.dtype != tdtype(dtype) or Wimg.ndim != 2 or Wimg.stride(-1) != 1 or Wimg.shape[0] < V or Wimg.shape[1] < D:
+        raise ValueError(f'vocab_weight_mean: W image must be (>= {V}, >= {D}) {tdtype(dtype)} with unit column stride, got {tuple(Wimg.shape)} {Wimg.dtype}')
+    if bias is None or bias.numel() < V or bias.device != Wimg.device:
+        raise ValueError(f'vocab_weight_mean: bias must hold {V} float32 on {Wimg.device}')
+    dev = Wimg.device
+    if wbar is None:
+        wbar = torch.empty((D,), device=dev, dtype=torch.float32)
+    if bbar is None:
+        bbar = torch.empty((1,), device=dev, dtype=torch.float32)
+    if wbar.numel() < D or bbar.numel() < 1 or wbar.device != dev or bbar.device != dev:
+        raise ValueError(f'vocab_weight_mean: wbar must hold {D} and bbar 1 float32 on {dev}')
+    lib = load()
+    words = lib.pk_vocab_weight_mean_words(dtype, V, D)
+    if workspace is None:
+        workspace = torch.empty((max(words, 1),), device=dev, dtype=torch.float32)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() < words or workspace.device != dev:
+        raise ValueError(f'vocab_weight_mean: workspace must be >= {words} contiguous float32 on {dev}')
+    rc = lib.pk_vocab_weight_mean(dtype, ptr(Wimg), Wimg.stride(0), f32p(bias, 'to_logits.bias'), V, D, f32p(wbar, 'wbar'), f32p(bbar, 'bbar'),
+                                  ptr(workspace), stream(Wimg))
+    _check(rc, 'pk_vocab_weight_mean')
+    return wbar, bbar
+
+
+def vocab_ce(dtype, partials, M, V, A, W, bias, D, targets, rows, loss, lse=None, *, label_smoothing=0., z_loss_weight=0., wbar=None, bbar=None):
+    """loss[m] = lse(logits[m]) - logits[m][targets[rows[m]]] from the partials of vocab_sample(..., need_lse=True); lse (M,) f32 optional.
+    label_smoothing / z_loss_weight: loss[m] = lse - (1 - eps) logit[target] - eps mean_v logit[m][v] + zeta lse^2 (pk_vocab_ce_reg), with
+    (wbar, bbar) of vocab_weight_mean on the same W / bias (needed when label_smoothing > 0); both zero: the plain call."""
+    if label_smoothing == 0. and z_loss_weight == 0.:
+        rc = load().pk_vocab_ce(dtype, ptr(partials), M, V, ptr(A), A.stride(-2), ptr(W), W.stride(0), f32p(bias, 'to_logits.bias'), D,
+                                ptr(targets), ptr(rows), ptr(loss), ptr(lse), stream(A))
+        _check(rc, 'pk_vocab_ce')
+        return
+    if wbar is not None and wbar.numel() < D:
+        raise ValueError(f'vocab_ce: wbar must hold {D} float32, got {tuple(wbar.shape)}')
+    rc = load().pk_vocab_ce_reg(dtype, ptr(partials), M, V, ptr(A), A.stride(-2), ptr(W), W.stride(0), f32p(bias, 'to_logits.bias'), D,
+                                ptr(targets), ptr(rows), ptr(loss), ptr(lse), float(label_smoothing), float(z_loss_weight),
+                                f32p(wbar, 'wbar'), f32p(bbar, 'bbar'), stream(A))
+    _check(rc, 'pk_vocab_ce_reg')
 
 
 def vocab_eval_words(M, V):
@@ -823,11 +881,19 @@ def vocab_eval(dtype, A, W, bias, M, V, D, targets, rows, *, pred=None, lse=None
     return workspace
 
 
-def ce_grad_slab(logits, lse, targets, rows, M, Vs, v0, scale, g, gT, db=None, scale_dev=None):
-    """g / gT <- (softmax - onehot) * scale [* scale_dev[0]] of one slab of vocabulary columns (see the header); logits (M, >= Vs) f32"""
-    rc = load().pk_ce_grad_slab(1 if g.dtype == torch.bfloat16 else 0, ptr(logits), logits.stride(0), ptr(lse), ptr(targets), ptr(rows), M, Vs, v0,
-                                float(scale), ptr(scale_dev), ptr(g), g.stride(0), ptr(gT), gT.stride(0), ptr(db), stream(logits))
-    _check(rc, 'pk_ce_grad_slab')
+def ce_grad_slab(logits, lse, targets, rows, M, Vs, v0, scale, g, gT, db=None, scale_dev=None, *, label_smoothing=0., z_loss_weight=0., V_total=0):
+    """g / gT <- (softmax - onehot) * scale [* scale_dev[0]] of one slab of vocabulary columns (see the header); logits (M, >= Vs) f32.
+    label_smoothing / z_loss_weight: g = (softmax (1 + 2 zeta lse) - (1 - eps) onehot - eps / V_total) * scale (pk_ce_grad_slab_reg), V_total the
+    whole vocabulary; both zero: the plain call."""
+    if label_smoothing == 0. and z_loss_weight == 0.:
+        rc = load().pk_ce_grad_slab(1 if g.dtype == torch.bfloat16 else 0, ptr(logits), logits.stride(0), ptr(lse), ptr(targets), ptr(rows), M, Vs, v0,
+                                    float(scale), ptr(scale_dev), ptr(g), g.stride(0), ptr(gT), gT.stride(0), ptr(db), stream(logits))
+        _check(rc, 'pk_ce_grad_slab')
+        return
+    rc = load().pk_ce_grad_slab_reg(1 if g.dtype == torch.bfloat16 else 0, ptr(logits), logits.stride(0), ptr(lse), ptr(targets), ptr(rows), M, Vs, v0,
+                                    float(scale), ptr(scale_dev), ptr(g), g.stride(0), ptr(gT), gT.stride(0), ptr(db),
+                                    float(label_smoothing), float(z_loss_weight), int(V_total), stream(logits))
+    _check(rc, 'pk_ce_grad_slab_reg')
 
 
 def topk_mask(scores, B, n, k, mask_id, mask, ids, rows_out=None, scores_next=None):

@@ -587,11 +587,15 @@ template <> __device__ __forceinline__ float w_elem<bf16x3>(const bf16x3* wrow, 
     return bf2f(blk[c & 31]) + bf2f(blk[32 + (c & 31)]);
 }
 
-template <typename T>
+// REG (label smoothing eps, z-loss weight zeta; pk_vocab_ce_reg): loss[m] = lse - (1 - eps) logit[target] - eps zbar + zeta lse^2, where
+// zbar = mean_v logit[m][v] = A[m] . wbar + bbar is one more D-long dot product against the column means pk_vocab_weight_mean left (wbar may be NULL
+// when eps == 0).  REG = false is the plain kernel: no extra argument is read, the arithmetic is unchanged.
+template <typename T, bool REG>
 __global__ __launch_bounds__(256) void vocab_ce_kernel(const float* __restrict__ p_max, const float* __restrict__ p_sum, int ntiles, int M,
                                                        const T* __restrict__ A, int lda, const T* __restrict__ W, int ldw,
                                                        const float* __restrict__ bias, int D, const long long* __restrict__ targets,
-                                                       const int* __restrict__ rows, float* __restrict__ loss, float* __restrict__ lse_out) {
+                                                       const int* __restrict__ rows, float* __restrict__ loss, float* __restrict__ lse_out,
+                                                       float eps, float zeta, const float* __restrict__ wbar, const float* __restrict__ bbar) {
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
@@ -611,11 +615,124 @@ __global__ __launch_bounds__(256) void vocab_ce_kernel(const float* __restrict__
     float dot = 0.f;
     for (int c = lane; c < D; c += 64) dot += load_elem(a + c) * w_elem<T>(w, c);
     dot = wave_sum(dot);
+    float zbar = 0.f;
+    if (REG && wbar) {
+        for (int c = lane; c < D; c += 64) zbar += load_elem(a + c) * wbar[c];
+        zbar = wave_sum(zbar) + bbar[0];
+    }
     if (lane == 0) {
         const float lse = gmax + logf(gsum);
-        loss[m] = lse - (dot + bias[tgt]);
+        if (REG) loss[m] = lse - (1.f - eps) * (dot + bias[tgt]) - eps * zbar + zeta * (lse * lse);
+        else loss[m] = lse - (dot + bias[tgt]);
         if (lse_out) lse_out[m] = lse;
     }
+}
+
+// ---- pk_vocab_weight_mean: wbar[c] = mean_v W[v][c] and bbar = mean_v bias[v], the operands of the label-smoothing term above ------------------
+// One streaming pass over the (V, ldw) operand image, read as the head's main loop reads it (w_elem: f32, bf16, or hi + lo of the split-bf16 planes).
+// Stage 1: a workgroup owns a contiguous range of rows; a thread owns one group of G columns (one 16-byte load: 4 f32, 8 bf16; split-bf16: 8 hi and
+// 8 lo halves, two 16-byte loads) and every RP-th row of the range, four rows in flight; the RP row-lanes of a column group meet in LDS and are folded
+// in ascending order into part[workgroup][column].  Stage 2: one thread per column folds the workgroups in ascending order; its last workgroup
+// takes the bias.  No atomics: the order of every sum is fixed by (V, D, dtype), two calls agree bit for bit.
+constexpr int WMEAN_MAX_BLOCKS = 1024;
+
+template <typename T> struct WMeanGroup { static constexpr int G = 4; };
+template <> struct WMeanGroup<bf16> { static constexpr int G = 8; };
+template <> struct WMeanGroup<bf16x3> { static constexpr int G = 8; };
+
+__device__ __forceinline__ void wmean_load(const float* wrow, int c0, float (&x)[4]) {
+    const float4 v = *reinterpret_cast<const float4*>(wrow + c0);
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+}
+__device__ __forceinline__ void wmean_load(const bf16* wrow, int c0, float (&x)[8]) {
+    const uint4 v = *reinterpret_cast<const uint4*>(wrow + c0);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x[2 * j] = bf2f((u16)(w[j] & 0xffffu)); x[2 * j + 1] = bf2f((u16)(w[j] >> 16)); }
+}
+// split-bf16: block c0 / 32 of the row holds 32 hi halves then 32 lo halves (c0 % 8 == 0: both loads are 16-byte aligned and inside the block)
+__device__ __forceinline__ void wmean_load(const bf16x3* wrow, int c0, float (&x)[8]) {
+    const u16* blk = reinterpret_cast<const u16*>(wrow + (c0 & ~31));
+    const uint4 h = *reinterpret_cast<const uint4*>(blk + (c0 & 31));
+    const uint4 l = *reinterpret_cast<const uint4*>(blk + 32 + (c0 & 31));
+    const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        x[2 * j] = bf2f((u16)(hw[j] & 0xffffu)) + bf2f((u16)(lw[j] & 0xffffu));
+        x[2 * j + 1] = bf2f((u16)(hw[j] >> 16)) + bf2f((u16)(lw[j] >> 16));
+    }
+}
+
+// grid (nblk, ceil(ncg / CG)); CG = min(ncg, 256) column groups per workgroup, RP = 256 / CG row-lanes; part [nblk][Dp], Dp = ncg * G
+template <typename T>
+__global__ __launch_bounds__(256) void weight_mean_partial_kernel(const T* __restrict__ W, int ldw, int V, int ncg, int CG, int rows_per_block,
+                                                                  float* __restrict__ part, int Dp) {
+    constexpr int G = WMeanGroup<T>::G;
+    __shared__ float red[256][G + 1];
+    const int RP = 256 / CG;
+    const int cl = threadIdx.x % CG, r = threadIdx.x / CG;
+    const int cg = blockIdx.y * CG + cl;
+    const bool live = r < RP && cg < ncg;
+    const int vbeg = blockIdx.x * rows_per_block, vend = min(V, vbeg + rows_per_block);
+    float acc[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) acc[j] = 0.f;
+    if (live) {
+        for (int v = vbeg + r; v < vend; v += 4 * RP) {
+            float x[4][G];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int vu = v + u * RP;
+                if (vu < vend) wmean_load(W + (size_t)vu * ldw, cg * G, x[u]);
+                else {
+#pragma unroll
+                    for (int j = 0; j < G; ++j) x[u][j] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int j = 0; j < G; ++j) acc[j] += x[u][j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j) red[threadIdx.x][j] = acc[j];
+    __syncthreads();
+    if (!live || r != 0) return;
+    for (int q = 1; q < RP; ++q)
+#pragma unroll
+        for (int j = 0; j < G; ++j) acc[j] += red[q * CG + cl][j];
+#pragma unroll
+    for (int j = 0; j < G; ++j) part[(size_t)blockIdx.x * Dp + cg * G + j] = acc[j];
+}
+
+// workgroups [0, gridDim.x - 1): wbar[c] = (sum over the nblk partial rows, ascending) / V; the last workgroup: bbar[0] = mean of the bias
+__global__ __launch_bounds__(256) void weight_mean_fold_kernel(const float* __restrict__ part, int nblk, int Dp, int D, int V,
+                                                               const float* __restrict__ bias, float* __restrict__ wbar, float* __restrict__ bbar) {
+    if (blockIdx.x + 1 < gridDim.x) {
+        const int c = blockIdx.x * 256 + threadIdx.x;
+        if (c >= D) return;
+        float s = 0.f;
+        int b = 0;
+        for (; b + 8 <= nblk; b += 8) {
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u) * Dp + c];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += x[u];
+        }
+        for (; b < nblk; ++b) s += part[(size_t)b * Dp + c];
+        wbar[c] = s / (float)V;
+        return;
+    }
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int v = threadIdx.x; v < V; v += 256) s += bias[v];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int q = 1; q < 256; ++q) s += red[q];
+    bbar[0] = s / (float)V;
 }
 
 // ---- pk_vocab_eval: the validation statistics of the vocab head in ONE pass over the vocabulary, still without the logits ----------------------
@@ -828,11 +945,13 @@ __global__ __launch_bounds__(256) void vocab_eval_reduce_kernel(const int* __res
 // recomputes the slab's logits with pk_gemm, turns them into g IN PLACE here -- also written transposed, the A operand of the dW GEMM --
 // and feeds both to pk_gemm (dE accumulates through the residual input).  Tile: 32 x 32 through LDS (coalesced both ways).
 // TO = float (exact-f32 / split-bf16 GEMMs read f32 A operands) or bf16.
-template <typename TO>
+// REG (pk_ce_grad_slab_reg): g = (p (1 + 2 zeta lse_m) - (1 - eps) [v == t_m] - eps / V_total) * scale, the gradient of the label-smoothed loss with the
+// z-loss term (V_total: the WHOLE vocabulary, not the slab).  REG = false is the plain kernel.
+template <typename TO, bool REG>
 __global__ __launch_bounds__(256) void ce_grad_slab_kernel(const float* __restrict__ logits, int ldl, const float* __restrict__ lse,
                                                            const long long* __restrict__ targets, const int* __restrict__ rows, int M, int Vs,
                                                            int v0, float scale_, const float* __restrict__ scale_dev, TO* __restrict__ g, int ldg,
-                                                           TO* __restrict__ gT, int ldgt) {
+                                                           TO* __restrict__ gT, int ldgt, float eps, float zeta, float inv_vtotal) {
     __shared__ float tile[32][33];
     const float scale = scale_dev ? scale_ * scale_dev[0] : scale_;       // the upstream gradient stays on the device (no host read in backward)
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;        // 32 x 8 threads, 4 rows each
@@ -843,7 +962,12 @@ __global__ __launch_bounds__(256) void ce_grad_slab_kernel(const float* __restri
         float x = 0.f;
         if (m < M && v < Vs) {
             const long long t = targets[rows ? rows[m] : m];
-            x = (__expf(logits[(size_t)m * ldl + v] - lse[m]) - (t == (long long)(v0 + v) ? 1.f : 0.f)) * scale;
+            if (REG) {
+                const float l = lse[m];
+                x = (__expf(logits[(size_t)m * ldl + v] - l) * (1.f + 2.f * zeta * l) - (t == (long long)(v0 + v) ? 1.f - eps : 0.f) - eps * inv_vtotal) * scale;
+            } else {
+                x = (__expf(logits[(size_t)m * ldl + v] - lse[m]) - (t == (long long)(v0 + v) ? 1.f : 0.f)) * scale;
+            }
             store_elem(g + (size_t)m * ldg + v, x);
         }
         tile[ml][tx] = x;
@@ -1021,45 +1145,109 @@ extern "C" int pk_vocab_reduce(const void* partials, int M, int V, const int* ro
     return PK_OK;
 }
 
-// loss[m] = logsumexp_v(logits[m][v]) - logits[m][targets[r]], r = rows ? rows[m] : m, from the partials of a pk_vocab_sample
-// call made with need_lse bit 0 set on the SAME A / W / bias (phenaki_pytorch.py:640-643 F.cross_entropy, reduction left to
-// the caller).  targets must be < V.
-extern "C" int pk_ce_grad_slab(int out_bf16, const float* logits, int ldl, const float* lse, const long long* targets, const int* rows,
-                               int M, int Vs, int v0, float scale, const float* scale_dev, void* g, int ldg, void* gT, int ldgt, float* db, void* stream) {
+// the regularised objective's arguments: eps in [0, 1), zeta >= 0, both finite
+static bool ce_reg_args_ok(float eps, float zeta) { return eps >= 0.f && eps < 1.f && zeta >= 0.f && zeta <= 3.0e38f; }
+
+// g of one slab (see ce_grad_slab_kernel); label_smoothing = z_loss_weight = 0 launches the plain kernel, V_total is then unused
+extern "C" int pk_ce_grad_slab_reg(int out_bf16, const float* logits, int ldl, const float* lse, const long long* targets, const int* rows,
+                                   int M, int Vs, int v0, float scale, const float* scale_dev, void* g, int ldg, void* gT, int ldgt, float* db,
+                                   float label_smoothing, float z_loss_weight, int V_total, void* stream) {
     if (!logits || !lse || !targets || !g || !gT || M <= 0 || Vs <= 0 || v0 < 0 || ldl < Vs || ldg < Vs || ldgt < M) return PK_EINVAL;
+    if (!ce_reg_args_ok(label_smoothing, z_loss_weight)) return PK_EINVAL;
+    const bool reg = label_smoothing > 0.f || z_loss_weight > 0.f;
+    if (reg && ((long long)v0 + Vs > (long long)V_total)) return PK_EINVAL;
+    const float eps = label_smoothing, zeta = z_loss_weight, inv_v = reg ? 1.0f / (float)V_total : 0.f;
     dim3 grid((Vs + 31) / 32, (ldgt + 31) / 32);
     hipStream_t s = STREAM(stream);
+#define PK_CG(TO, REG) hipLaunchKernelGGL((ce_grad_slab_kernel<TO, REG>), grid, dim3(256), 0, s, logits, ldl, lse, targets, rows, M, Vs, v0, scale, scale_dev, \
+                                          reinterpret_cast<TO*>(g), ldg, reinterpret_cast<TO*>(gT), ldgt, eps, zeta, inv_v)
     if (out_bf16) {
-        hipLaunchKernelGGL((ce_grad_slab_kernel<bf16>), grid, dim3(256), 0, s, logits, ldl, lse, targets, rows, M, Vs, v0, scale, scale_dev,
-                           reinterpret_cast<bf16*>(g), ldg, reinterpret_cast<bf16*>(gT), ldgt);
+        if (reg) PK_CG(bf16, true); else PK_CG(bf16, false);
         if (db) hipLaunchKernelGGL((rowsum_kernel<bf16>), dim3((Vs + 3) / 4), dim3(256), 0, s, reinterpret_cast<const bf16*>(gT), ldgt, Vs, M, db);
     } else {
-        hipLaunchKernelGGL((ce_grad_slab_kernel<float>), grid, dim3(256), 0, s, logits, ldl, lse, targets, rows, M, Vs, v0, scale, scale_dev,
-                           reinterpret_cast<float*>(g), ldg, reinterpret_cast<float*>(gT), ldgt);
+        if (reg) PK_CG(float, true); else PK_CG(float, false);
         if (db) hipLaunchKernelGGL((rowsum_kernel<float>), dim3((Vs + 3) / 4), dim3(256), 0, s, reinterpret_cast<const float*>(gT), ldgt, Vs, M, db);
     }
+#undef PK_CG
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_ce_grad_slab(int out_bf16, const float* logits, int ldl, const float* lse, const long long* targets, const int* rows,
+                               int M, int Vs, int v0, float scale, const float* scale_dev, void* g, int ldg, void* gT, int ldgt, float* db, void* stream) {
+    return pk_ce_grad_slab_reg(out_bf16, logits, ldl, lse, targets, rows, M, Vs, v0, scale, scale_dev, g, ldg, gT, ldgt, db, 0.f, 0.f, 0, stream);
+}
+
+// loss[m] = logsumexp_v(logits[m][v]) - logits[m][targets[r]], r = rows ? rows[m] : m, from the partials of a pk_vocab_sample
+// call made with need_lse bit 0 set on the SAME A / W / bias (phenaki_pytorch.py:640-643 F.cross_entropy, reduction left to
+// the caller).  targets must be < V.  With label_smoothing / z_loss_weight: see vocab_ce_kernel.
+extern "C" int pk_vocab_ce_reg(int dtype, const void* partials, int M, int V, const void* A, int lda, const void* W, int ldw,
+                               const float* bias, int D, const long long* targets, const int* rows, float* loss, float* lse_out,
+                               float label_smoothing, float z_loss_weight, const float* wbar, const float* bbar, void* stream) {
+    if (!partials || !A || !W || !bias || !targets || !loss || M <= 0 || V <= 0 || D <= 0) return PK_EINVAL;
+    if (dtype != 0 && dtype != 1 && dtype != 2) return PK_EINVAL;
+    if (!ce_reg_args_ok(label_smoothing, z_loss_weight)) return PK_EINVAL;
+    if (label_smoothing > 0.f && (!wbar || !bbar)) return PK_EINVAL;
+    const bool reg = label_smoothing > 0.f || z_loss_weight > 0.f;
+    const float eps = label_smoothing, zeta = z_loss_weight;
+    const float* wb = label_smoothing > 0.f ? wbar : nullptr;           // eps == 0: the means are not read
+    const int ntiles = pk_vocab_ntiles(V);
+    const size_t sz = (size_t)ntiles * M;
+    const float* f = reinterpret_cast<const float*>(partials);
+    const dim3 grid((M + 3) / 4);
+#define PK_VC(TT, REG) hipLaunchKernelGGL((vocab_ce_kernel<TT, REG>), grid, dim3(256), 0, STREAM(stream), f + 3 * sz, f + 4 * sz, ntiles, M, \
+                                          reinterpret_cast<const TT*>(A), lda, reinterpret_cast<const TT*>(W), ldw, bias, D, targets, rows, loss, lse_out, \
+                                          eps, zeta, wb, bbar)
+    if (dtype == 2) { if (reg) PK_VC(bf16x3, true); else PK_VC(bf16x3, false); }
+    else if (dtype == 1) { if (reg) PK_VC(bf16, true); else PK_VC(bf16, false); }
+    else { if (reg) PK_VC(float, true); else PK_VC(float, false); }
+#undef PK_VC
     PK_CHECK_LAUNCH();
     return PK_OK;
 }
 
 extern "C" int pk_vocab_ce(int dtype, const void* partials, int M, int V, const void* A, int lda, const void* W, int ldw,
                            const float* bias, int D, const long long* targets, const int* rows, float* loss, float* lse_out, void* stream) {
-    if (!partials || !A || !W || !bias || !targets || !loss || M <= 0 || V <= 0 || D <= 0) return PK_EINVAL;
+    return pk_vocab_ce_reg(dtype, partials, M, V, A, lda, W, ldw, bias, D, targets, rows, loss, lse_out, 0.f, 0.f, nullptr, nullptr, stream);
+}
+
+// geometry of pk_vocab_weight_mean, shared by the workspace size and the launch: G columns per thread, ncg column groups, nblk row ranges
+static void weight_mean_geom(int dtype, int V, int D, int& G, int& ncg, int& CG, int& nblk, int& rpb) {
+    G = dtype == 0 ? 4 : 8;
+    ncg = (D + G - 1) / G;
+    CG = ncg < 256 ? ncg : 256;
+    const int RP = 256 / CG;
+    nblk = (V + RP - 1) / RP;
+    if (nblk > WMEAN_MAX_BLOCKS) nblk = WMEAN_MAX_BLOCKS;
+    rpb = (V + nblk - 1) / nblk;
+    nblk = (V + rpb - 1) / rpb;                                         // no empty workgroup
+}
+
+// workspace of pk_vocab_weight_mean in 4-byte words
+extern "C" int pk_vocab_weight_mean_words(int dtype, int V, int D) {
+    if (V <= 0 || D <= 0 || D > (1 << 20) || (dtype != 0 && dtype != 1 && dtype != 2)) return 0;
+    int G, ncg, CG, nblk, rpb;
+    weight_mean_geom(dtype, V, D, G, ncg, CG, nblk, rpb);
+    return nblk * ncg * G;                                              // <= 1024 row ranges x (D + 7)
+}
+
+extern "C" int pk_vocab_weight_mean(int dtype, const void* W, int ldw, const float* bias, int V, int D, float* wbar, float* bbar,
+                                    void* workspace, void* stream) {
+    if (!W || !bias || !wbar || !bbar || !workspace || V <= 0 || D <= 0 || D > (1 << 20) || ldw < D) return PK_EINVAL;
     if (dtype != 0 && dtype != 1 && dtype != 2) return PK_EINVAL;
-    const int ntiles = pk_vocab_ntiles(V);
-    const size_t sz = (size_t)ntiles * M;
-    const float* f = reinterpret_cast<const float*>(partials);
-    const dim3 grid((M + 3) / 4);
-    if (dtype == 2) {
-        hipLaunchKernelGGL((vocab_ce_kernel<bf16x3>), grid, dim3(256), 0, STREAM(stream), f + 3 * sz, f + 4 * sz, ntiles, M,
-                           reinterpret_cast<const bf16x3*>(A), lda, reinterpret_cast<const bf16x3*>(W), ldw, bias, D, targets, rows, loss, lse_out);
-        PK_CHECK_LAUNCH();
-        return PK_OK;
-    }
-    if (dtype == 1) hipLaunchKernelGGL((vocab_ce_kernel<bf16>), grid, dim3(256), 0, STREAM(stream), f + 3 * sz, f + 4 * sz, ntiles, M,
-                                       reinterpret_cast<const bf16*>(A), lda, reinterpret_cast<const bf16*>(W), ldw, bias, D, targets, rows, loss, lse_out);
-    else hipLaunchKernelGGL((vocab_ce_kernel<float>), grid, dim3(256), 0, STREAM(stream), f + 3 * sz, f + 4 * sz, ntiles, M,
-                            reinterpret_cast<const float*>(A), lda, reinterpret_cast<const float*>(W), ldw, bias, D, targets, rows, loss, lse_out);
+    const int eps = dtype == 1 ? 8 : 4;
+    if ((D % eps) || (ldw % eps) || !al16(W)) return PK_EALIGN;
+    if (dtype == 2 && (ldw & 31)) return PK_EALIGN;                     // the planes come in whole blocks of 32 columns, rows start on a block
+    int G, ncg, CG, nblk, rpb;
+    weight_mean_geom(dtype, V, D, G, ncg, CG, nblk, rpb);
+    const int Dp = ncg * G;
+    float* part = reinterpret_cast<float*>(workspace);
+    const dim3 grid(nblk, (ncg + CG - 1) / CG);
+    hipStream_t s = STREAM(stream);
+    if (dtype == 1) hipLaunchKernelGGL((weight_mean_partial_kernel<bf16>), grid, dim3(256), 0, s, reinterpret_cast<const bf16*>(W), ldw, V, ncg, CG, rpb, part, Dp);
+    else if (dtype == 2) hipLaunchKernelGGL((weight_mean_partial_kernel<bf16x3>), grid, dim3(256), 0, s, reinterpret_cast<const bf16x3*>(W), ldw, V, ncg, CG, rpb, part, Dp);
+    else hipLaunchKernelGGL((weight_mean_partial_kernel<float>), grid, dim3(256), 0, s, reinterpret_cast<const float*>(W), ldw, V, ncg, CG, rpb, part, Dp);
+    hipLaunchKernelGGL(weight_mean_fold_kernel, dim3((D + 255) / 256 + 1), dim3(256), 0, s, part, nblk, Dp, D, V, bias, wbar, bbar);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

@@ -351,8 +351,16 @@ class Phenaki(PackedModule):
     def __init__(self, *, maskgit: MaskGit, cvivit: CViViT, critic=None, steps=18, t5_name=DEFAULT_T5_NAME,
                  sample_temperature=0., text_embed_dim=None, cond_drop_prob=0.25, max_text_len=128,
                  self_token_critic=False, critic_loss_weight=1., critic_noise_anneal_schedule='decay',
-                 critic_train_sample_temperature=1.):
+                 critic_train_sample_temperature=1., label_smoothing=0., z_loss_weight=0., train_cond_drop=False):
+        """label_smoothing (eps in [0, 1)) and z_loss_weight (zeta >= 0) regularise the masked-token cross entropy of the training objective:
+        mean_m [lse_m - (1 - eps) z_m[t_m] - eps mean_v z_m[v] + zeta lse_m^2] (train.py::vocab_cross_entropy); `evaluate` keeps the plain nll.
+        train_cond_drop=True makes classifier-free-guidance dropout fire in the training step with probability `cond_drop_prob` (the reference
+        shadows it with 0 at phenaki_pytorch.py:594, see train.py::phenaki_loss).  All three are off by default: the reference's objective."""
         super().__init__()
+        self.label_smoothing, self.z_loss_weight = L.check_ce_regularisers(label_smoothing, z_loss_weight, 'Phenaki')
+        if not isinstance(train_cond_drop, bool):
+            raise ValueError(f'Phenaki: train_cond_drop must be a bool, got {train_cond_drop!r}')
+        self.train_cond_drop = train_cond_drop
         assert isinstance(maskgit, MaskGit) and isinstance(cvivit, CViViT)
         assert critic is None or isinstance(critic, (TokenCritic, SelfCritic))
         self.cvivit = cvivit.copy_for_eval()
@@ -395,6 +403,32 @@ class Phenaki(PackedModule):
             from .train import phenaki_loss
             return phenaki_loss(self, *args, **kwargs)
         return self.objective_value(*args, **kwargs)
+
+    def _cond_drop_masks(self, text_mask, cond_drop_prob, draws, b, need_critic):
+        """(MaskGit's text mask, the critic's text mask) of one training call.  train_cond_drop off, or an unconditional model: both are
+        `text_mask` itself and no random number is drawn.  On: cond_drop_prob = default(argument, self.cond_drop_prob), and MaskGit and the
+        critic each AND their own prob_mask_like((b,), 1 - p) into it (phenaki_pytorch.py:188-189 through SelfCritic or MaskGit, :286-287 in a
+        TokenCritic that attends to the text); draws['cond_keep'] / draws['critic_cond_keep'] ((b,) bool) replace the two draws."""
+        if not self.train_cond_drop or self.unconditional or not exists(text_mask):
+            return text_mask, text_mask
+        p = float(default(cond_drop_prob, self.cond_drop_prob))
+        if not 0. <= p <= 1.:
+            raise ValueError(f'cond_drop_prob must be in [0, 1], got {cond_drop_prob!r}')
+        device = text_mask.device
+
+        def dropped(key):
+            if key in draws:
+                keep = draws[key].to(device).bool().reshape(b)
+            elif p > 0:
+                keep = prob_mask_like((b,), 1 - p, device=device)
+            else:
+                return text_mask
+            return keep[:, None] & text_mask
+
+        mg_mask = dropped('cond_keep')
+        critic = self.critic
+        critic_uses_text = need_critic and exists(critic) and (isinstance(critic, SelfCritic) or critic.has_cross_attn)
+        return mg_mask, (dropped('critic_cond_keep') if critic_uses_text else text_mask)
 
     def _masked_batch(self, videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws, mask_prob=None, generator=None):
         """the inputs of the training call -> (ids (b, n) int64, patch shape, text_embeds, text_mask, video_mask, mask (b, n) bool, masked ids): the
@@ -453,9 +487,10 @@ class Phenaki(PackedModule):
         token-critic BCE).  Forward only: the result carries no autograd graph (the backward kernels are SURVEY.md 8f
         "next").  The 65 536-way logits are never written: pk_vocab_sample draws the critic's input ids and leaves the
         softmax statistics, pk_vocab_ce turns them into per-row losses.  As in the reference, `cond_drop_prob` has no
-        effect on this path (it is shadowed by `cond_drop_prob = 0` at :594).
+        effect on this path (it is shadowed by `cond_drop_prob = 0` at :594) unless the model was built with train_cond_drop=True
+        (`_cond_drop_masks`); label_smoothing / z_loss_weight apply as in the training step, so the two return the same number.
         _draws (tests): dict(rand_step (b,), perm_noise (b,n) U[0,1), gumbel_u (b,n,V) U[0,1)) replaces the three
-        random draws of the reference (:620, :626 -> :43-55, :653)."""
+        random draws of the reference (:620, :626 -> :43-55, :653); cond_keep / critic_cond_keep (b,) bool the two of train_cond_drop."""
         assert not (only_train_generator and only_train_critic)
         assert not (only_train_critic and not exists(self.critic)), 'only_train_critic needs a critic (Phenaki(critic=...) or self_token_critic=True)'
         mg, critic = self.maskgit, self.critic
@@ -467,11 +502,12 @@ class Phenaki(PackedModule):
 
         dt = compute_dtype_of(mg)
         D, V = mg.dim, mg.to_logits.weight.shape[0]
-        e = mg.embeds(masked_input, video_patch_shape=patch_shape, context=text_embeds, text_mask=text_mask, video_mask=video_mask)
+        need_critic = exists(critic) and not only_train_generator
+        mg_text_mask, critic_text_mask = self._cond_drop_masks(text_mask, cond_drop_prob, draws, b, need_critic)
+        e = mg.embeds(masked_input, video_patch_shape=patch_shape, context=text_embeds, text_mask=mg_text_mask, video_mask=video_mask)
         # rows of the vocab head: the critic's labels compare the ids with the gumbel-sampled prediction at EVERY position
         # (phenaki_pytorch.py:653,671), so with a critic the head runs on all b*n rows; the generator-only objective needs
         # the masked rows only (>= 1 per sample, clamp(min=1) above)
-        need_critic = exists(critic) and not only_train_generator
         flat_mask = mask_token_mask.reshape(-1)
         rows = None if need_critic else flat_mask.nonzero().reshape(-1).int()
         M = b * n if need_critic else rows.numel()
@@ -486,7 +522,10 @@ class Phenaki(PackedModule):
         loss = None
         if not only_train_critic:
             loss_rows = torch.empty((M,), device=device, dtype=torch.float32)
-            L.vocab_ce(dt, partials, M, V, mixed, w_logits, mg.to_logits.bias, D, ids.reshape(-1), rows, loss_rows)
+            eps, zeta = self.label_smoothing, self.z_loss_weight
+            wbar, bbar = L.vocab_weight_mean(dt, w_logits, mg.to_logits.bias, V, D) if eps > 0. else (None, None)
+            L.vocab_ce(dt, partials, M, V, mixed, w_logits, mg.to_logits.bias, D, ids.reshape(-1), rows, loss_rows,
+                       label_smoothing=eps, z_loss_weight=zeta, wbar=wbar, bbar=bbar)
             loss = (loss_rows[flat_mask] if need_critic else loss_rows).mean()
         if not need_critic:
             return loss
@@ -494,7 +533,7 @@ class Phenaki(PackedModule):
         L.vocab_reduce(partials, M, V, None, None, None, pred, None, False)
         pred = pred.view(b, n)
         critic_input = torch.where(mask_token_mask, pred, ids)
-        crit = critic(critic_input.view(b, *patch_shape), video_mask=video_mask, cond_drop_prob=0., text_mask=text_mask,
+        crit = critic(critic_input.view(b, *patch_shape), video_mask=video_mask, cond_drop_prob=0., text_mask=critic_text_mask,
                       context=text_embeds)
         labels = (ids != pred).float()
         critic_loss = torch.nn.functional.binary_cross_entropy_with_logits(crit.reshape(b, n), labels)

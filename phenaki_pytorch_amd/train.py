@@ -15,6 +15,7 @@ Every block of the trunk is ONE torch.autograd.Function whose forward and backwa
     _LayerNormFn    norm_out                                                   pk_layernorm        / pk_layernorm_bwd
     _PositionBias   ContinuousPositionBias as (heads, n, n)                    relative-position-table MLP + pk_bias_gather / pk_bias_scatter
     _VocabCrossEntropy   to_logits + cross entropy on the masked rows          pk_vocab_sample, pk_vocab_ce / pk_ce_grad_slab + pk_gemm
+                         (+ label smoothing / z-loss, off by default)          pk_vocab_weight_mean, pk_vocab_ce_reg / pk_ce_grad_slab_reg
     _BCEHead        critic to_logits / to_pred + BCE-with-logits               pk_bce_head
 
 Activations and gradients are f32 in HBM (288 GB: every block keeps what its backward needs instead of recomputing it); the GEMMs run in the
@@ -645,8 +646,11 @@ class _VocabCrossEntropy(torch.autograd.Function):
     """mean over the selected rows of CE(E[rows] W^T + b, targets[rows]); the (rows, V) logits are never stored (phenaki_pytorch.py:640-643)"""
 
     @staticmethod
-    def forward(ctx, embeds, weight, bias, targets, rows, dtype, slab, imgs=None, shared=None):
-        """imgs: (image of W, image of W^T) from `linear_images` (already refreshed), else packed here.  shared: (partials, M_all) of a
+    def forward(ctx, embeds, weight, bias, targets, rows, dtype, slab, imgs=None, shared=None, reg=(0., 0.)):
+        """reg = (label_smoothing eps, z_loss_weight zeta): mean_m [lse_m - (1 - eps) z_m[t_m] - eps mean_v z_m[v] + zeta lse_m^2]; (0, 0) is the
+        plain cross entropy and launches what it always did.  The mean logit is A_m . wbar + bbar with the column means of the SAME operand image
+        (pk_vocab_weight_mean, one pass over it, only when eps > 0); backward does not need them.
+        imgs: (image of W, image of W^T) from `linear_images` (already refreshed), else packed here.  shared: (partials, M_all) of a
         pk_vocab_sample call with need_lse over ALL rows of `embeds` on the same weight image (the critic's gumbel sampling of the training step,
         phenaki_pytorch.py:653-655): its per-tile (max, sum-exp) statistics are temperature- and noise-free, so the rows of this loss take theirs
         from it instead of a second pass over the vocabulary."""
@@ -681,11 +685,14 @@ class _VocabCrossEntropy(torch.autograd.Function):
             L.vocab_sample(dtype, A, Wp, b, M, V, D, 1.0, None, None, 0, True, partials, no_noise=True)
         loss_rows = torch.empty((M,), device=dev, dtype=torch.float32)
         lse = torch.empty((M,), device=dev, dtype=torch.float32)
-        L.vocab_ce(dtype, partials, M, V, A, Wp, b, D, tg, rows, loss_rows, lse=lse)
+        eps, zeta = reg
+        wbar, bbar = L.vocab_weight_mean(dtype, Wp, b, V, D) if eps > 0. else (None, None)
+        L.vocab_ce(dtype, partials, M, V, A, Wp, b, D, tg, rows, loss_rows, lse=lse, label_smoothing=eps, z_loss_weight=zeta, wbar=wbar, bbar=bbar)
         # A (the gathered operand rows) and Wp (the packed vocabulary weight: 64-134 MB at V = 65 536) go through save_for_backward like the rest,
         # so they are released when autograd frees the saved tensors and take part in its version checks
         ctx.save_for_backward(E, weight, b, tg, lse, rows, A, Wp)
         ctx.dtype, ctx.slab, ctx.has_bias, ctx.Wt = dtype, slab, bias is not None, (imgs[1] if imgs is not None else None)
+        ctx.reg = (eps, zeta)
         return L.colsum(loss_rows.view(M, 1), M, 1, torch.empty((1,), device=dev, dtype=torch.float32), scale=1.0 / M).reshape(())
 
     @staticmethod
@@ -717,7 +724,8 @@ class _VocabCrossEntropy(torch.autograd.Function):
             Vs = min(slab, V - v0)
             # logits of the slab: the same A / W rows / bias as the forward pass (rows [v0, v0 + Vs) of the packed weight)
             L.gemm(dtype, A, Wp[v0:v0 + Vs], M, Vs, D, C=logits, bias=b[v0:v0 + Vs], ldc=logits.stride(0))
-            L.ce_grad_slab(logits, lse, tg, rows, M, Vs, v0, scale, g, gT, db=db[v0:v0 + Vs], scale_dev=gdev)
+            L.ce_grad_slab(logits, lse, tg, rows, M, Vs, v0, scale, g, gT, db=db[v0:v0 + Vs], scale_dev=gdev,
+                           label_smoothing=ctx.reg[0], z_loss_weight=ctx.reg[1], V_total=V)
             # dE (+)= g @ W_slab: contraction over the slab's columns = columns [v0, v0 + Vs) of the W^T image (k offset on the operand)
             L.gemm(dtype, g, Wt[:, v0:], M, D, Vs, C=dE, res=None if first else dE, lda=g.stride(0))
             # dW_slab = g^T @ E (K = the rows, padded to the k-tile: gT's pad columns are zeroed by the kernel, E^T is zero-padded)
@@ -727,7 +735,7 @@ class _VocabCrossEntropy(torch.autograd.Function):
             full = _zeros((R, D), dev)
             L.scatter_rows(dE, rows, full, M, D)
             dE = full
-        return dE, dW, (db if ctx.has_bias else None), None, None, None, None, None, None
+        return dE, dW, (db if ctx.has_bias else None), None, None, None, None, None, None, None
 
 
 class _Linear(torch.autograd.Function):
@@ -796,13 +804,17 @@ class _BCEHead(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------------------------ modules -> blocks
 
-def vocab_cross_entropy(embeds, weight, bias, targets, compute_dtype='bf16x3', slab=2048, rows=None):
+def vocab_cross_entropy(embeds, weight, bias, targets, compute_dtype='bf16x3', slab=2048, rows=None, label_smoothing=0., z_loss_weight=0.):
     """mean_m CE(embeds[r_m] @ weight^T + bias, targets[r_m]) with gradients for embeds / weight / bias; logits never stored.
     embeds (R, D) f32 on the HIP device, weight (V, D), bias (V,) or None, targets (R,) int64 in [0, V); rows (M,) int32: the rows r_m the
-    loss is taken over (None: all).  slab: vocabulary columns per backward step (a multiple of 64)."""
+    loss is taken over (None: all).  slab: vocabulary columns per backward step (a multiple of 64).
+    label_smoothing eps in [0, 1) and z_loss_weight zeta >= 0 (both off by default): with z_m the logits of row m,
+        mean_m [lse_m - (1 - eps) z_m[t_m] - eps mean_v z_m[v] + zeta lse_m^2]
+    = F.cross_entropy(z, t, label_smoothing=eps) + zeta * mean(logsumexp(z)^2), the PaLM z-loss; ValueError outside those ranges."""
+    reg = L.check_ce_regularisers(label_smoothing, z_loss_weight)
     assert slab % 64 == 0 and slab > 0
     assert weight.shape[0] % 8 == 0 and weight.shape[1] % 8 == 0, 'vocabulary size and embedding width must be multiples of 8'
-    return _VocabCrossEntropy.apply(embeds, weight, bias, targets, rows, resolve_dtype(compute_dtype), int(slab), None, None)
+    return _VocabCrossEntropy.apply(embeds, weight, bias, targets, rows, resolve_dtype(compute_dtype), int(slab), None, None, reg)
 
 
 def layernorm_train(ln: LayerNorm, x2d):
@@ -930,8 +942,11 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
                  only_train_generator=False, only_train_critic=False, _draws=None):
     """phenaki_pytorch.py:562-687 with an autograd graph over the MaskGit / critic parameters (the C-ViViT and the T5 encoder are frozen there
     too).  _draws (tests): dict(rand_step, perm_noise, gumbel_u) replaces the three random draws, as in `Phenaki.objective_value`.
-    `cond_drop_prob` is accepted for signature compatibility and HAS NO EFFECT: the reference overwrites it with 0 before use
-    (phenaki_pytorch.py:594 shadows the argument), so classifier-free-guidance dropout never fires in its training step either."""
+    `cond_drop_prob` HAS NO EFFECT by default: the reference overwrites it with 0 before use (phenaki_pytorch.py:594 shadows the argument), so
+    classifier-free-guidance dropout never fires in its training step either.  Phenaki(train_cond_drop=True) runs what that code does without the
+    shadowing: cond_drop_prob = default(argument, ph.cond_drop_prob), and MaskGit and the critic EACH draw their own prob_mask_like((b,), 1 - p)
+    (:188-189, :286-287) and AND it into the text mask (_draws: 'cond_keep' / 'critic_cond_keep', (b,) bool).  An unconditional model ignores the flag.
+    ph.label_smoothing / ph.z_loss_weight regularise the masked-token cross entropy (`vocab_cross_entropy`); the critic's BCE is unchanged."""
     from .phenaki import SelfCritic, TokenCritic
     require_train_dim_head(ph.maskgit, ph.critic)                       # before the tokenizer or anything else launches
     assert not (only_train_generator and only_train_critic)
@@ -986,12 +1001,13 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
             # the flat positions of the masked tokens in ascending order, with a size the host already knows (no nonzero() read-back)
             rows = torch.argsort((~mask_token_mask).reshape(-1).to(torch.uint8), stable=True)[:M_rows].int()
         masked_input = torch.where(mask_token_mask, ph.mask_id, ids)
+        mg_text_mask, critic_text_mask = ph._cond_drop_masks(text_mask, cond_drop_prob, draws, b, exists(critic) and not only_train_generator)
 
     dt = compute_dtype_of(mg)
     D, V = mg.dim, mg.to_logits.weight.shape[0]
     ctx_mg = torch.no_grad() if only_train_critic else torch.enable_grad()
     with ctx_mg:
-        e = trunk_train(mg, masked_input, patch_shape, context=text_embeds, text_mask=text_mask, video_mask=video_mask, use_bias=True,
+        e = trunk_train(mg, masked_input, patch_shape, context=text_embeds, text_mask=mg_text_mask, video_mask=video_mask, use_bias=True,
                         use_cross=not mg.unconditional, alpha=mg.gradient_shrink_alpha)
     loss = None
     need_critic = exists(critic) and not only_train_generator
@@ -1016,7 +1032,7 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
             L.vocab_sample(dt, A, w_logits, mg.to_logits.bias.detach(), M, V, D, float(ph.critic_train_sample_temperature), U, None, seed, share, partials)
     if not only_train_critic:
         loss = _VocabCrossEntropy.apply(e, mg.to_logits.weight, mg.to_logits.bias, ids.reshape(-1), rows, dt, CE_SLAB, head.pair if head is not None else None,
-                                        (partials, M) if (need_critic and share) else None)
+                                        (partials, M) if (need_critic and share) else None, (ph.label_smoothing, ph.z_loss_weight))
     if not need_critic:
         return loss
     with torch.no_grad():
@@ -1026,12 +1042,12 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
         critic_input = torch.where(mask_token_mask, pred, ids)
         labels = (ids != pred).float().reshape(-1).contiguous()
     if isinstance(critic, SelfCritic):
-        ce = trunk_train(critic.maskgit, critic_input, patch_shape, context=text_embeds, text_mask=text_mask, video_mask=video_mask, use_bias=True,
+        ce = trunk_train(critic.maskgit, critic_input, patch_shape, context=text_embeds, text_mask=critic_text_mask, video_mask=video_mask, use_bias=True,
                          use_cross=not critic.maskgit.unconditional, alpha=critic.maskgit.gradient_shrink_alpha)
         head = critic.to_pred[0]
     else:
         assert isinstance(critic, TokenCritic)
-        ce = trunk_train(critic, critic_input, patch_shape, context=text_embeds if critic.has_cross_attn else None, text_mask=text_mask,
+        ce = trunk_train(critic, critic_input, patch_shape, context=text_embeds if critic.has_cross_attn else None, text_mask=critic_text_mask,
                          video_mask=video_mask, use_bias=False, use_cross=critic.has_cross_attn, alpha=1.0)
         head = critic.to_logits[0]
     critic_loss = _BCEHead.apply(ce, head.weight, head.bias, labels)
