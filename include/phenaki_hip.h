@@ -41,7 +41,8 @@ extern "C" {
  * attention.py:243-252 (CPB MLP, act 2 = LeakyReLU(0.1); act 3 = ReLU: the VGG16 classifier, cvivit.py:349-352), cvivit.py:276,283 (patch embed), cvivit.py:328,333
  * (to_pixels), phenaki_pytorch.py:147 (to_logits).
  * A [M][lda] is f32 (a_is_f32) or T; W [N][ldw] is T; bias [N] f32 or NULL; res [M][ldr] f32 or NULL;
- * C is f32 (out_is_f32) or T; a_rows (or NULL) gathers A rows: logical row m reads A[a_rows[m]]. */
+ * C is f32 (out_is_f32) or T; a_rows (or NULL) gathers A rows: logical row m reads A[a_rows[m]].
+ * act 1 (GEGLU) with a residual is refused (PK_EINVAL): the pair is stored before the residual add, and no call site wants the fusion. */
 int pk_gemm(int dtype, int a_is_f32, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
             const float* bias, const float* res, int ldr, void* C, int ldc, int out_is_f32, int act,
             const int* a_rows, void* stream);

@@ -323,6 +323,7 @@ def gemm_form(dtype, A, W, M, N, K, **kw):
 def gemm(dtype, A, W, M, N, K, *, C, bias=None, res=None, act=ACT_NONE, a_rows=None, lda=None, ldc=None, variant=0, C2=None, ln=None,
          scatter=None, stats_out=None, ln_stats=None, dup_rows=0):
     """C = act(A @ W^T + bias) (+ res).  A: (rows, K) f32 or T; W: (N, Kpad) T; C preallocated.
+    act = ACT_GEGLU with a residual is refused (PK_EINVAL): the epilogues store the GEGLU pair before the residual add.
     a_rows gathers rows of A (A.shape[0] physical rows bound the DMA descriptor).
     C2: optional bf16 copy of an f32 C.  ln = (s, t, eps): the LayerNorm in front of this Linear folded in (A = the un-normalised
     rows, W = gamma (.) W, s / t its (N,) correction vectors).  scatter = (row_off (M,) int32, col_off (N,) int32): element (m, n) is

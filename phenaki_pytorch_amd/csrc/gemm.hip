@@ -658,6 +658,7 @@ static int gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const void* 
     if (dtype != 1 && !a_is_f32) return PK_EINVAL;               // exact-f32 and split-bf16 modes keep every activation f32
     if (dtype == 2 && C2) return PK_EINVAL;      // the bf16 copy is a bf16-mode feature (split-bf16 consumers read the f32 rows themselves)
     if (act == ACT_GEGLU && (N & 1)) return PK_EINVAL;
+    if (act == ACT_GEGLU && res) return PK_EINVAL;               // both epilogues store the GEGLU pair before the residual add: refused, not dropped
     if (a_rows && a_nrows <= 0) return PK_EINVAL;
     if (!a_rows) a_nrows = M;
     // k-rotation (gemm_dma.hpp): measured +12..33 % on the 65536-wide vocab-head shape, -0..13 % on the N <= 2736 shapes
