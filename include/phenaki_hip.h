@@ -441,6 +441,27 @@ int pk_ce_grad_slab_reg(int out_bf16, const float* logits, int ldl, const float*
  * masked rows pk_vocab_reduce overwrites afterwards. */
 int pk_topk_mask(const float* scores, int B, int n, int k, long long mask_id, unsigned char* mask, long long* ids,
                  int* rows_out, float* scores_next, void* stream);
+/* pk_topk_mask with an exclusion mask and a per-row k: the re-masking step of infilling (Phenaki.sample(known_ids=, known_mask=)).
+ *   k, row_off : device int32[B]; row_off is required when rows_out is given.
+ *   known      : device uint8[B][n], nonzero = keep the token; NULL = nothing is excluded.
+ *   scores     : NULL = all scores equal, so the rank of a free position is its index among the row's free positions (step 0: with
+ *                k[b] = the row's free count this masks and lists every free position, a pure compaction).
+ * mask[b][i] = 1 iff position i is free and fewer than k[b] FREE positions of row b rank before it (larger score, ties to the lower
+ * index), 0 elsewhere, known positions included.  Known positions are excluded by index, not by score value: they are never ranked,
+ * never counted in another position's rank, never masked, and their ids are never written.  ids = mask_id where masked, untouched
+ * elsewhere.  rows_out[row_off[b] + rank] = b*n + i; nothing is written outside [row_off[b], row_off[b] + k[b]).  scores_next (B*n, or
+ * NULL; must not alias scores) is -1e4 at EVERY position, as in pk_topk_mask.  Same geometry as pk_topk_mask (grid (B, ceil(n/64)), four
+ * lanes per position, the row and its known bytes in 5 n bytes of dynamic LDS: n <= 12288).
+ * PK_EINVAL before any launch: NULL k / mask / ids, B <= 0, n <= 0, n > 12288, rows_out without row_off, scores_next == scores.
+ * k[b] above the row's free count cannot be seen without a device read: the caller guarantees k[b] <= free count (then every slot of
+ * the row's rows_out range is written); the Python wrapper checks it where it holds the host counts. */
+int pk_topk_mask_keep(const float* scores, int B, int n, const int* k, const int* row_off, const unsigned char* known,
+                      long long mask_id, unsigned char* mask, long long* ids, int* rows_out, float* scores_next, void* stream);
+/* Infill compositing (Phenaki.infill(composite=True)): out[b][c][p] = mask[b][p] ? gen[b][c][p] : src[b][c][p] over (B, C, P) f32 with
+ * P = F*H*W pixels per channel; mask is uint8 (mask_batch, P) with mask_batch == B or 1 (shared by the batch).  A select: where the mask
+ * is 0 the output holds the source's bits.  out is a buffer of its own. */
+int pk_composite_mask(const float* gen, const float* src, const unsigned char* mask, float* out, int B, int C, long long P,
+                      int mask_batch, void* stream);
 
 /* phenaki_pytorch.py:246-263, 523-545: critic head Linear(dim,1) + CFG mix + noise_mult * (u - 0.5), prime dropped.
  * u [nb][n] U[0,1) draws, or NULL: drawn in the kernel from the counter hash of seed (+ *seed_dev, see pk_vocab_sample). */

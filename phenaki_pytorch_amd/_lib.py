@@ -90,6 +90,8 @@ SIGNATURES = {
     'pk_ce_grad_slab': [_I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _P],
     'pk_ce_grad_slab_reg': [_I, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _I, _P, _I, _P, _F, _F, _I, _P],
     'pk_topk_mask': [_P, _I, _I, _I, _LL, _P, _P, _P, _P, _P],
+    'pk_topk_mask_keep': [_P, _I, _I, _P, _P, _P, _LL, _P, _P, _P, _P, _P],
+    'pk_composite_mask': [_P, _P, _P, _P, _I, _I, _LL, _I, _P],
     'pk_critic_head': [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _F, _ULL, _P, _P, _P],
     'pk_pack': [_P, _LL, _P, _I, _I, _I, _P, _LL, _I, _I, _P],
     'pk_scatter_rows': [_P, _LL, _P, _P, _LL, _I, _I, _P],
@@ -900,6 +902,43 @@ def ce_grad_slab(logits, lse, targets, rows, M, Vs, v0, scale, g, gT, db=None, s
 def topk_mask(scores, B, n, k, mask_id, mask, ids, rows_out=None, scores_next=None):
     rc = load().pk_topk_mask(ptr(scores), B, n, k, mask_id, ptr(mask), ptr(ids), ptr(rows_out), ptr(scores_next), stream(scores))
     _check(rc, 'pk_topk_mask')
+
+
+def topk_mask_keep(scores, B, n, k, row_off, known, mask_id, mask, ids, rows_out=None, scores_next=None, k_host=None, free_host=None):
+    """pk_topk_mask_keep (see the header): per-row k and ragged row_off as device int32 (B,), known uint8 (B, n) or None, scores f32 (B, n) or
+    None (all equal: rank = index among the free positions).  k_host / free_host: the host copies of k and of the rows' free counts, where the
+    caller holds them -- k[b] > free count is refused here (the kernel cannot see it without a device read)."""
+    for name, t, want, numel in (('k', k, torch.int32, B), ('row_off', row_off, torch.int32, B), ('known', known, torch.uint8, B * n),
+                                 ('scores', scores, torch.float32, B * n), ('scores_next', scores_next, torch.float32, B * n),
+                                 ('mask', mask, torch.uint8, B * n), ('ids', ids, torch.int64, B * n), ('rows_out', rows_out, torch.int32, 0)):
+        if t is not None and (t.dtype != want or not t.is_contiguous() or t.numel() < numel or t.device != mask.device):
+            raise ValueError(f'topk_mask_keep: {name} must be >= {numel} contiguous {want} on {mask.device}, got {tuple(t.shape)} {t.dtype} on {t.device}')
+    if k_host is not None and free_host is not None:
+        if len(k_host) != B or len(free_host) != B or any(kb < 0 or kb > fb for kb, fb in zip(k_host, free_host)):
+            raise ValueError(f'topk_mask_keep: k = {list(k_host)} must lie in [0, free count] = {list(free_host)} per row')
+        if rows_out is not None and rows_out.numel() < sum(k_host):
+            raise ValueError(f'topk_mask_keep: rows_out holds {rows_out.numel()} entries, the rows need {sum(k_host)}')
+    rc = load().pk_topk_mask_keep(ptr(scores), B, n, ptr(k), ptr(row_off), ptr(known), mask_id, ptr(mask), ptr(ids), ptr(rows_out), ptr(scores_next),
+                                  stream(mask))
+    _check(rc, 'pk_topk_mask_keep')
+
+
+def composite_mask(gen, src, mask, out):
+    """out = where(mask, gen, src): gen / src / out (B, C, F, H, W) contiguous f32, mask (B | 1, F, H, W) contiguous uint8 broadcast over the
+    channels (pk_composite_mask).  A select: outside the mask the output holds src's bits."""
+    if gen.shape != src.shape or out.shape != src.shape or src.ndim != 5:
+        raise ValueError(f'composite_mask: gen / src / out must share one (B, C, F, H, W) shape, got {tuple(gen.shape)}, {tuple(src.shape)}, {tuple(out.shape)}')
+    B, C = src.shape[:2]
+    if mask.dtype != torch.uint8 or mask.ndim != 4 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != tuple(src.shape[2:]) or not mask.is_contiguous():
+        raise ValueError(f'composite_mask: mask must be contiguous uint8 ({B} | 1, F, H, W) = (.., {tuple(src.shape[2:])}), got {tuple(mask.shape)} {mask.dtype}')
+    for t, name in ((gen, 'gen'), (src, 'src'), (out, 'out')):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != src.device:
+            raise ValueError(f'composite_mask: {name} must be contiguous float32 on {src.device}, got {t.dtype} on {t.device}')
+        require_device(t, name)
+    if mask.device != src.device or out.data_ptr() in (gen.data_ptr(), src.data_ptr()):
+        raise ValueError('composite_mask: mask on the operands\' device and out a buffer of its own')
+    rc = load().pk_composite_mask(ptr(gen), ptr(src), ptr(mask), ptr(out), B, C, src[0, 0].numel(), mask.shape[0], stream(src))
+    _check(rc, 'pk_composite_mask')
 
 
 def critic_head(x, w, b, D, nb, n_tot, n_prime, has_null, scale, u, noise_mult, out, seed=0, seed_dev=None):

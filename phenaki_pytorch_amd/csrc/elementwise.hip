@@ -312,6 +312,18 @@ __global__ __launch_bounds__(256) void gated_gelu_tanh_kernel(const float* __res
     }
 }
 
+// infill compositing: out[b][c][p] = m[b][p] ? gen[b][c][p] : src[b][c][p], the (F, H, W) pixel mask broadcast over the channels (and over
+// the batch when it has one row).  A select, no arithmetic: pixels outside the mask are the source's bits.
+__global__ __launch_bounds__(256) void composite_mask_kernel(const float* __restrict__ gen, const float* __restrict__ src,
+                                                             const unsigned char* __restrict__ m, float* __restrict__ out,
+                                                             int C, long P, int mask_batch, long total) {
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long p = idx % P;
+        const long b = idx / (P * C);
+        out[idx] = m[(mask_batch == 1 ? 0 : b) * P + p] ? gen[idx] : src[idx];
+    }
+}
+
 // ---- the cache-policy mask (common.hpp): PK_CACHE_POLICY is the default, pk_set_cache_policy replaces it for the launches that follow.
 // Built-in default: non-temporal video loads in the wide patch kernel, the one site that won its A/B on MI355X (-16 ... -54 us of the batch-8
 // encode step); every store site and the other two load sites measured at or behind their plain form and stay plain (profiles/cache_policy.txt).
@@ -448,6 +460,15 @@ extern "C" int pk_critic_head(const float* x, int ldx, const float* w, const flo
     const int rows = nb * (n_tot - n_prime);
     hipLaunchKernelGGL(critic_head_kernel, dim3((rows + 3) / 4), dim3(256), 0, STREAM(stream), x, ldx, w, b, D, nb, n_tot, n_prime,
                        has_null, scale, u, noise_mult, seed, seed_dev, out);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_composite_mask(const float* gen, const float* src, const unsigned char* mask, float* out, int B, int C, long long P,
+                                 int mask_batch, void* stream) {
+    if (!gen || !src || !mask || !out || B <= 0 || C <= 0 || P <= 0 || (mask_batch != 1 && mask_batch != B)) return PK_EINVAL;
+    const long total = (long)B * C * P;
+    hipLaunchKernelGGL(composite_mask_kernel, dim3(nblocks(total)), dim3(256), 0, STREAM(stream), gen, src, mask, out, C, (long)P, mask_batch, total);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

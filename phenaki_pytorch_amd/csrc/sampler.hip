@@ -1022,6 +1022,48 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict_
     if (sel && rows_out) rows_out[(size_t)b * k + rank] = b * n + i;         // compacted list of the masked positions
 }
 
+// topk_mask_kernel with an exclusion mask and a per-row k (infilling: known tokens stay, the free ones are re-masked).  Same
+// geometry; the known bytes sit in LDS behind the scores.  A known position is excluded BY INDEX: it adds nothing to any rank and
+// is never selected, whatever its score.  scores == NULL: all scores equal, so rank = index among the free positions (step 0: mask
+// every free position of a row and list it, a pure compaction).  rows_out is ragged: row b owns [row_off[b], row_off[b] + k[b]).
+// The ranking loop is topk_mask_kernel's own: a known position's score is STAGED as NaN, and both ordered compares (w > v, w == v) are
+// false against a NaN, so it counts in nobody's rank without a byte read or a branch per compare (with `!kn[j] && ...` in the loop the
+// compiler kept a branch and a ds_read_u8 per element and gave up the 8-wide unrolled ds_read2_b32 form: 19.5 us against 5.9 us at
+// B = 8, n = 576).  Whether position i itself may be selected is decided from its known byte, not from its staged score.
+__global__ __launch_bounds__(256) void topk_mask_keep_kernel(const float* __restrict__ scores, int n, const int* __restrict__ k,
+                                                             const int* __restrict__ row_off, const unsigned char* __restrict__ known,
+                                                             long long mask_id, unsigned char* __restrict__ mask, long long* __restrict__ ids,
+                                                             int* __restrict__ rows_out, float* __restrict__ scores_next) {
+    extern __shared__ float sc[];
+    unsigned char* kn = reinterpret_cast<unsigned char*>(sc + n);
+    const int b = blockIdx.x;
+    const int kb = k[b], off = rows_out ? row_off[b] : 0;                    // uniform: scalar loads, in flight during the ranking
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const bool kw = known && known[(size_t)b * n + i] != 0;
+        const float s = scores ? scores[(size_t)b * n + i] : 0.f;
+        sc[i] = kw ? __builtin_nanf("") : s;
+        kn[i] = kw ? 1 : 0;
+    }
+    __syncthreads();
+    const int i = blockIdx.y * 64 + (threadIdx.x >> 2), part = threadIdx.x & 3;
+    const int q = (n + 3) >> 2;
+    const int j0 = part * q, j1 = j0 + q < n ? j0 + q : n;
+    const float v = i < n ? sc[i] : 0.f;
+    int rank = 0;
+    for (int j = j0; j < j1; ++j) {
+        const float w = sc[j];
+        rank += (w > v || (w == v && j < i)) ? 1 : 0;
+    }
+    rank += __shfl_xor(rank, 1, 64);
+    rank += __shfl_xor(rank, 2, 64);
+    if (part != 0 || i >= n) return;
+    if (scores_next) scores_next[(size_t)b * n + i] = -1e4f;                 // at EVERY position, as in topk_mask_kernel
+    const bool sel = !kn[i] && rank < kb;
+    mask[(size_t)b * n + i] = sel ? 1 : 0;
+    if (sel) ids[(size_t)b * n + i] = mask_id;
+    if (sel && rows_out) rows_out[(size_t)off + rank] = b * n + i;
+}
+
 }  // namespace pk
 using namespace pk;
 
@@ -1305,6 +1347,16 @@ extern "C" int pk_topk_mask(const float* scores, int B, int n, int k, long long 
                             long long* ids, int* rows_out, float* scores_next, void* stream) {
     if (!scores || !mask || !ids || B <= 0 || n <= 0 || k < 0 || n > 12288 || scores_next == scores) return PK_EINVAL;
     hipLaunchKernelGGL(topk_mask_kernel, dim3(B, (n + 63) / 64), dim3(256), n * sizeof(float), STREAM(stream), scores, n, k, mask_id, mask, ids, rows_out, scores_next);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_topk_mask_keep(const float* scores, int B, int n, const int* k, const int* row_off, const unsigned char* known,
+                                 long long mask_id, unsigned char* mask, long long* ids, int* rows_out, float* scores_next, void* stream) {
+    if (!k || !mask || !ids || B <= 0 || n <= 0 || n > 12288 || (rows_out && !row_off) || (scores && scores_next == scores)) return PK_EINVAL;
+    // the row's scores and its known bytes: 5 n <= 61 440 bytes of dynamic LDS
+    hipLaunchKernelGGL(topk_mask_keep_kernel, dim3(B, (n + 63) / 64), dim3(256), n * (sizeof(float) + 1), STREAM(stream),
+                       scores, n, k, row_off, known, mask_id, mask, ids, rows_out, scores_next);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

@@ -59,6 +59,71 @@ def mask_schedule(num_tokens, steps):
     return ks
 
 
+def infill_schedule(free_counts, steps):
+    """the per-sample schedule of an infilling sample(): with F_b free (regenerated) tokens in sample b, k_b(0) = F_b and
+    k_b(s) = mask_schedule(F_b, steps)[s] for s >= 1 (<= F_b always: cos <= 1 and F_b >= 1).  Returns host lists (ks, offs, totals):
+    ks[s][b], the exclusive prefix sums offs[s][b] = sum_{b' < b} ks[s][b'] (where sample b's rows start in the compact row list) and
+    totals[s] = sum_b ks[s][b] (the rows the vocabulary head visits at step s)."""
+    per_count = {F: mask_schedule(F, steps) for F in set(free_counts)}
+    ks, offs, totals = [], [], []
+    for s in range(steps):
+        row = [F if s == 0 else per_count[F][s] for F in free_counts]
+        off, acc = [], 0
+        for k in row:
+            off.append(acc)
+            acc += k
+        ks.append(row)
+        offs.append(off)
+        totals.append(acc)
+    return ks, offs, totals
+
+
+def pixel_to_token_mask(pixel_mask, temporal_patch_size, patch_size):
+    """(b, F, H, W) bool pixel mask -> (b, f, h, w) bool token mask: a token is marked iff ANY pixel of its footprint is.  Token frame 0 is
+    video frame 0; token frame t >= 1 covers video frames 1 + (t-1) pt .. t pt; spatially the footprint is the ph x pw patch."""
+    ph, pw = patch_size
+    pt = temporal_patch_size
+    b, F, H, W = pixel_mask.shape
+    sp = pixel_mask.reshape(b, F, H // ph, ph, W // pw, pw).any(dim=5).any(dim=3)
+    rest = sp[:, 1:].reshape(b, (F - 1) // pt, pt, H // ph, W // pw).any(dim=2)
+    return torch.cat((sp[:, :1], rest), dim=1)
+
+
+def token_to_pixel_mask(token_mask, temporal_patch_size, patch_size):
+    """(b, f, h, w) bool token mask -> (b, F, H, W) bool: every token's footprint (the inverse layout of pixel_to_token_mask)"""
+    ph, pw = patch_size
+    sp = token_mask.repeat_interleave(ph, dim=2).repeat_interleave(pw, dim=3)
+    return torch.cat((sp[:, :1], sp[:, 1:].repeat_interleave(temporal_patch_size, dim=1)), dim=1)
+
+
+def _check_known(known_ids, known_mask, B, patch_shape, V, device):
+    """validate sample()'s known_ids / known_mask (ValueError) and lay them out: ids (B, n) int64 and known (B, n) uint8, contiguous on
+    `device`, plus the host list of free counts F_b -- read with the ONE host synchronisation of an infilling call (the range check of the
+    known ids rides on the same transfer)."""
+    n = patch_shape[0] * patch_shape[1] * patch_shape[2]
+    if not (torch.is_tensor(known_ids) and torch.is_tensor(known_mask)):
+        raise ValueError('sample: known_ids and known_mask must be tensors')
+    if known_ids.dtype != torch.int64:
+        raise ValueError(f'sample: known_ids must be int64 token ids, got {known_ids.dtype}')
+    if known_mask.dtype != torch.bool:
+        raise ValueError(f'sample: known_mask must be bool (True = keep the token), got {known_mask.dtype}')
+    grid = tuple(patch_shape)
+    if tuple(known_ids.shape) not in ((B, *grid), (B, n)):
+        raise ValueError(f'sample: known_ids must be {(B, *grid)} or {(B, n)}, got {tuple(known_ids.shape)}')
+    if tuple(known_mask.shape) not in ((B, *grid), (B, n), grid, (n,)):
+        raise ValueError(f'sample: known_mask must be {(B, *grid)}, {(B, n)}, {grid} or {(n,)}, got {tuple(known_mask.shape)}')
+    ids = known_ids.to(device).reshape(B, n).contiguous()
+    known = known_mask.to(device)
+    known = known.reshape(1, n).expand(B, n) if known.ndim in (1, 3) else known.reshape(B, n)
+    bad = (known & ((ids < 0) | (ids >= V))).sum().reshape(1)
+    *free, nbad = torch.cat(((~known).sum(dim=1), bad)).tolist()
+    if nbad:
+        raise ValueError(f'sample: {nbad} known token ids lie outside [0, {V})')
+    if min(free) < 1:
+        raise ValueError(f'sample: every sample needs at least one token to generate, free counts {free}')
+    return ids, known.to(torch.uint8).contiguous(), free
+
+
 def _u8(mask):
     if mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous()):
         return mask
@@ -622,6 +687,7 @@ class Phenaki(PackedModule):
         ids, mask, pred, scores2 = st['ids'], st['mask'], st['pred'], st['scores']
         rows_buf, partials, mixed = st['rows'], st['partials'], st['mixed']
         ks, steps = st['ks'], self.steps
+        known = st.get('known')                                         # infilling (sample(known_ids=, known_mask=)): uint8 (B, n), else None
         noise_fn, trace, seed_dev = st['noise_fn'], st['trace'], st['seed_dev']
         seed_base = st['seed_base'] if seed_dev is None else 0          # graph mode: the base seed lives in *seed_dev
         M64 = 0xFFFFFFFFFFFFFFFF
@@ -636,7 +702,15 @@ class Phenaki(PackedModule):
             cur, nxt = scores2[step & 1], scores2[(step + 1) & 1]
 
             rows, M = None, B * n
-            if step > 0 and have_scores:
+            if known is not None:
+                # infilling: re-mask among the FREE positions only, k_b(s) of them in sample b (known tokens are excluded by index, whatever
+                # their score); step 0 has no scores and k_b = F_b: it masks every free position and lists it, so the head never visits a
+                # known row.  The compact list is ragged: sample b's rows start at offs[s][b], M(s) = sum_b k_b(s) rows in all
+                if st['compact']:
+                    rows, M = rows_buf, st['totals'][step]
+                L.topk_mask_keep(cur if step > 0 else None, B, n, st['ks_dev'][step], st['offs_dev'][step], known, self.mask_id, mask, ids, rows,
+                                 scores_next=nxt if need_lse else None, k_host=ks[step], free_host=ks[0])
+            elif step > 0 and have_scores:
                 # mask + ids = where(mask, mask_id, ids); only the k_s re-masked positions need the vocab head this step
                 # (predictions elsewhere are discarded, phenaki_pytorch.py:509) -> compact row list for the head
                 if st['compact']:
@@ -710,22 +784,52 @@ class Phenaki(PackedModule):
                     partials=torch.empty((5 * L.vocab_ntiles(V) * B * n,), device=device, dtype=torch.float32),
                     mixed=torch.empty((B * n, D), device=device, dtype=L.tdtype(dt)))
 
+    def _sample_start(self, st, known_ids, known):
+        """the loop's starting state, in place (the buffers are a captured graph's static inputs): everything masked; or, when infilling,
+        the caller's ids and known bytes -- step 0's pk_topk_mask_keep then lays the mask_id over the free positions"""
+        if known is None:
+            st['ids'].fill_(self.mask_id)
+            st['mask'].fill_(1)
+        else:
+            st['ids'].copy_(known_ids)
+            st['known'].copy_(known)
+
     @eval_decorator
     @torch.no_grad()
     def sample(self, *, num_frames, texts=None, prime_frames=None, batch_size=1, cond_scale=3.,
                starting_temperature=0.9, noise_K=1., _noise_fn=None, _trace=None, _return_ids=False, _compact=None, _seed=None,
-               _force_fn=None, _prime_ids=None):
+               _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None):
         """phenaki_pytorch.py:418-560.  `_noise_fn(kind, step, shape)` (tests) injects the U[0,1) draws of the
         reference run ('gumbel' (B,n,V) and 'critic' (B,n), device f32 tensors); _noise_fn='torch': torch's device generator in the
         reference's order (a seeded reference run on the same GPU draws the same noise); without it the noise comes from the
         in-kernel counter hash seeded from torch's default (CPU) generator (`_seed`: the exact 64-bit stream seed instead;
         the seed a call used is kept in `self._pk_last_seed`).  `_force_fn(step, ids, mask)` (tests) may overwrite a step's masked
         input ids (B, n) int64 and mask (B, n) uint8 in place before the trunk runs (teacher forcing; eager, no row compaction);
-        `_prime_ids` (tests, with prime_frames given) replaces the token ids the tokenizer would produce for the prime frames."""
+        `_prime_ids` (tests, with prime_frames given) replaces the token ids the tokenizer would produce for the prime frames.
+
+        Infilling: `known_ids` (int64 token ids) and `known_mask` (bool, True = keep the token), both or neither, shaped (B, f, h, w) or
+        (B, n) for (f, h, w) = get_video_patch_shape(num_frames); the mask may also be (f, h, w) or (n,), shared by the batch.  The known
+        tokens stay as given and are part of the decoded clip; only the free ones are sampled: the loop starts from
+        where(known, known_ids, mask_id), re-masks k_b(s) = mask_schedule(F_b, steps)[s] of sample b's F_b free tokens per step
+        (pk_topk_mask_keep: known positions are excluded by index, whatever the critic scores them) and the vocabulary head visits only
+        masked rows (sum_b F_b at step 0).  Not combined with prime_frames.  B is len(texts), or batch_size without texts.  Shape, dtype
+        and range errors (known ids outside [0, num_tokens), a sample with nothing to generate) are ValueErrors raised before anything
+        launches.  The free counts F_b are read from the device once per call: ONE host synchronisation that a plain call does not have.
+        With enable_sample_graph the counts are part of the configuration key: another mask with the same counts replays, other counts
+        capture again."""
         device = next(self.parameters()).device
         L.require_device(next(self.parameters()), 'Phenaki parameters')
         mg, critic = self.maskgit, self.critic
         dt = compute_dtype_of(mg)
+        known = free_counts = None
+        if exists(known_ids) or exists(known_mask):
+            if not (exists(known_ids) and exists(known_mask)):
+                raise ValueError('sample: give known_ids and known_mask together (or neither)')
+            if exists(prime_frames):
+                raise ValueError('sample: known_ids / known_mask cannot be combined with prime_frames')
+            nb = (1 if isinstance(texts, str) else len(texts)) if exists(texts) else batch_size
+            known_ids, known, free_counts = _check_known(known_ids, known_mask, nb, self.cvivit.get_video_patch_shape(num_frames),
+                                                         mg.to_logits.weight.shape[0], device)
         if isinstance(_noise_fn, str):
             # _noise_fn = 'torch': the reference's own noise -- torch's device generator, consumed in the reference's order (per step one
             # uniform_ of (B, n, V) for gumbel_sample, phenaki_pytorch.py:88-93, then one of (B, n) for the critic scores, :69-70 / :541-543).
@@ -788,7 +892,7 @@ class Phenaki(PackedModule):
         use_graph = self.__dict__.get('_pk_sample_graph', False) and _noise_fn is None and _trace is None and _force_fn is None
         key = (B, n, prime_token_length, prime_num_frames, tuple(patch_shape), None if text_embeds is None else tuple(text_embeds.shape),
                float(cond_scale), float(starting_temperature), float(noise_K), compact, dt, str(device), self.steps,
-               self.critic_noise_anneal_schedule)
+               self.critic_noise_anneal_schedule, None if known is None else tuple(free_counts))
         graphs = self.__dict__.setdefault('_pk_sample_graphs', {}) if use_graph else None
         entry = graphs.get(key) if use_graph else None
         # a captured graph holds raw pointers to the live parameters AND to the packed copies derived from them: any change of a
@@ -811,8 +915,7 @@ class Phenaki(PackedModule):
                     st['c_tm_r'].copy_(_cfg_masks(entry['tm'], B, c_null))
             if has_prime:
                 st['prime_ids'].copy_(prime_token_ids)
-            st['ids'].fill_(self.mask_id)
-            st['mask'].fill_(1)
+            self._sample_start(st, known_ids, known)
             st['seed_dev'].fill_(seed_base)
             entry['graph'].replay()
             video = entry['video'] if self.__dict__.get('_pk_sample_graph_static') else entry['video'].clone()
@@ -826,8 +929,11 @@ class Phenaki(PackedModule):
                   noise_fn=_noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base, seed_dev=None, with_null=with_null, c_null=c_null,
                   ctx_r=rep(text_embeds).contiguous() if has_ctx else None, tm_r=_cfg_masks(text_mask, B, with_null) if has_ctx else None,
                   c_ctx_r=crep(text_embeds).contiguous() if c_has_ctx else None, c_tm_r=_cfg_masks(text_mask, B, c_null) if c_has_ctx else None)
-        st['ids'].fill_(self.mask_id)
-        st['mask'].fill_(1)
+        if known is not None:
+            ks, offs, totals = infill_schedule(free_counts, self.steps)
+            st.update(ks=ks, totals=totals, known=torch.empty_like(known), ks_dev=torch.tensor(ks, dtype=torch.int32, device=device),
+                      offs_dev=torch.tensor(offs, dtype=torch.int32, device=device))
+        self._sample_start(st, known_ids, known)
         if not use_graph:
             video = self._sample_loop(st)
             return (video, st['ids']) if _return_ids else video
@@ -841,8 +947,7 @@ class Phenaki(PackedModule):
         with torch.cuda.stream(side):
             self._sample_loop(st)
         torch.cuda.current_stream(device).wait_stream(side)
-        st['ids'].fill_(self.mask_id)
-        st['mask'].fill_(1)
+        self._sample_start(st, known_ids, known)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             entry['video'] = self._sample_loop(st)
@@ -851,6 +956,52 @@ class Phenaki(PackedModule):
         graph.replay()
         video = entry['video'] if self.__dict__.get('_pk_sample_graph_static') else entry['video'].clone()
         return (video, st['ids'].clone()) if _return_ids else video
+
+
+    @eval_decorator
+    @torch.no_grad()
+    def infill(self, video, edit_mask, *, texts=None, mask_level='pixel', composite=False, **sample_kwargs):
+        """regenerate a region of a clip and keep the rest: inpainting / outpainting (a spatial region), frame interpolation or extension in
+        either direction (whole frames), in token space.  `video` (B, C, F, H, W) float32; `edit_mask` bool, True = regenerate:
+          mask_level='pixel': (B | 1, F, H, W).  A token is regenerated iff ANY pixel of its footprint is marked: token frame 0 is video
+                              frame 0, token frame t >= 1 covers frames 1 + (t-1) pt .. t pt, spatially the ph x pw patch;
+          mask_level='token': (B | 1, f, h, w) over get_video_patch_shape(F), taken as it is.
+        The clip is tokenised, the tokens outside the edit region become sample()'s known tokens (the one host synchronisation and the
+        graph key of `sample(known_ids=, known_mask=)` apply; other keyword arguments go to sample) and the decoded clip, ALL frames, is
+        returned.  The known tokens were computed from the ORIGINAL clip -- the tokenizer attends spatially and causally in time, so a known
+        token may carry traces of the pixels that are being replaced, and kept regions come back as the tokenizer reconstructs them (the
+        usual token-space inpainting).  composite=True returns where(edit pixels, decoded, video) instead (pk_composite_mask): pixels
+        outside the mask are the input's bits; the pixel mask is the caller's at mask_level='pixel', the tokens' footprint at 'token'."""
+        cv = self.cvivit
+        if mask_level not in ('pixel', 'token'):
+            raise ValueError(f"infill: mask_level must be 'pixel' or 'token', got {mask_level!r}")
+        if not torch.is_tensor(video) or video.ndim != 5 or video.dtype != torch.float32:
+            raise ValueError('infill: video must be a (B, C, F, H, W) float32 tensor')
+        if 'prime_frames' in sample_kwargs or 'known_ids' in sample_kwargs or 'known_mask' in sample_kwargs or 'num_frames' in sample_kwargs:
+            raise ValueError('infill: prime_frames / known_ids / known_mask / num_frames are not arguments of infill')
+        B, C, F, H, W = video.shape
+        pt = cv.temporal_patch_size
+        if (H, W) != tuple(cv.image_size) or (F - 1) % pt:
+            raise ValueError(f'infill: video must be {tuple(cv.image_size)} pixels with 1 + a multiple of {pt} frames, got {(F, H, W)}')
+        grid = tuple(cv.get_video_patch_shape(F))
+        want = (F, H, W) if mask_level == 'pixel' else grid
+        if not torch.is_tensor(edit_mask) or edit_mask.dtype != torch.bool:
+            raise ValueError('infill: edit_mask must be a bool tensor (True = regenerate)')
+        if edit_mask.ndim != 4 or edit_mask.shape[0] not in (1, B) or tuple(edit_mask.shape[1:]) != want:
+            raise ValueError(f'infill: a {mask_level} edit_mask must be ({B} | 1, {", ".join(map(str, want))}), got {tuple(edit_mask.shape)}')
+        edit_mask = edit_mask.to(video.device)
+        token_edit = pixel_to_token_mask(edit_mask, pt, cv.patch_size) if mask_level == 'pixel' else edit_mask
+        ids = cv(video, return_only_codebook_ids=True).reshape(B, -1)
+        known_mask = ~token_edit
+        out = self.sample(num_frames=F, texts=texts, batch_size=B, known_ids=ids, known_mask=known_mask[0] if known_mask.shape[0] == 1 else known_mask,
+                          **sample_kwargs)
+        if not composite:
+            return out
+        decoded = out[0] if isinstance(out, tuple) else out
+        pixel_edit = edit_mask if mask_level == 'pixel' else token_to_pixel_mask(edit_mask, pt, cv.patch_size)
+        mixed = torch.empty_like(video, memory_format=torch.contiguous_format)
+        L.composite_mask(decoded.contiguous(), video.contiguous(), pixel_edit.to(torch.uint8).contiguous(), mixed)
+        return (mixed, *out[1:]) if isinstance(out, tuple) else mixed
 
 
 def make_video(phenaki: Phenaki, texts: List[str], num_frames, prime_lengths):
