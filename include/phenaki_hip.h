@@ -353,6 +353,16 @@ int pk_attn_small(const float* q, int ldq, const float* kv, int ldkv, const floa
  * (flat b * (n_tot - n_prime) + i). */
 int pk_cfg_mix(const float* x, int ldx, int nb, int n_tot, int n_prime, const int* rows, int nrows, float scale,
                int has_null, void* out, int ldo, int out_is_f32, int D, void* stream);
+/* pk_cfg_mix for P conditional branches and a base branch (phenaki_pytorch.py:149-161 generalised: negative prompts, prompt blends,
+ * per-sample guidance scales).  x holds (P + has_base) * nb sequences laid out [cond_0 | .. | cond_{P-1} | base], the order of pk_cfg_mix's
+ * [cond | null].  coef: device f32 [(P + 1) * nb], the table row of the current step: rows 0..P-1 hold the blend weights a[k][b], row P the
+ * guidance scale g[b].  Per sample b:
+ *     cbar = e_0 (P == 1: no multiply)  |  sum_k a[k][b] e_k, k ascending (P > 1);      out = e_base + (cbar - e_base) * g[b]
+ * has_base == 0 writes cbar alone (a blend at scale 1; row P of coef is not read).  rows / nrows / n_prime / out_is_f32 / the 16-byte
+ * accesses are pk_cfg_mix's; the mix is its f32 expression: P == 1 is bit-identical to pk_cfg_mix at equal scales.
+ * PK_EINVAL before any launch: P outside 1..3, coef == NULL, D % 4 != 0, has_base == 0 with P == 1. */
+int pk_guidance_mix(const float* x, int ldx, int nb, int n_tot, int n_prime, const int* rows, int nrows, const float* coef, int P,
+                    int has_base, void* out, int ldo, int out_is_f32, int D, void* stream);
 
 /* phenaki_pytorch.py:213 + 88-93 + 506-509 + 547-550, never materialising logits: per row
  * pred = argmax(logits / max(T,1e-10) + gumbel(U)), optional (max, sum exp) for 1 - softmax[pred].
@@ -468,6 +478,13 @@ int pk_composite_mask(const float* gen, const float* src, const unsigned char* m
 int pk_critic_head(const float* x, int ldx, const float* w, const float* b, int D, int nb, int n_tot, int n_prime,
                    int has_null, float scale, const float* u, float noise_mult, unsigned long long seed,
                    const unsigned long long* seed_dev, float* out, void* stream);
+/* pk_critic_head with pk_guidance_mix's table in place of scale / has_null (phenaki_pytorch.py:251-263 generalised): the head's scalar
+ * outputs s_k of the rows [cond_0 | .. | cond_{P-1} | base] are mixed by the same formula, s = s_0 | sum_k a[k][b] s_k, then
+ * s_base + (s - s_base) * g[b]; the row dot product is the device function pk_critic_head uses, so P == 1 is bit-identical to it.
+ * Noise (u, the counter hash, seed_dev) as in pk_critic_head.  PK_EINVAL as pk_guidance_mix. */
+int pk_critic_head_guided(const float* x, int ldx, const float* w, const float* b, int D, int nb, int n_tot, int n_prime,
+                          const float* coef, int P, int has_base, const float* u, float noise_mult, unsigned long long seed,
+                          const unsigned long long* seed_dev, float* out, void* stream);
 
 /* ---- training step, SURVEY.md 8f row 1: backward of the MaskGit / TokenCritic trunk (phenaki_pytorch.py:562-687 under autograd; host side
  * phenaki_pytorch_amd/train.py).  Activations and gradients are f32; the matrix products are pk_gemm calls on operands laid down by pk_pack.

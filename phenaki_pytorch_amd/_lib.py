@@ -76,6 +76,7 @@ SIGNATURES = {
     'pk_attn_fwd_lse_dh': [_I, _I, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     'pk_attn_small': [_P, _I, _P, _I, _P, _P, _F, _P, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     'pk_cfg_mix': [_P, _I, _I, _I, _I, _P, _I, _F, _I, _P, _I, _I, _I, _P],
+    'pk_guidance_mix': [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P],
     'pk_vocab_ntiles': [_I],
     'pk_vocab_sample_philox': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _ULL, _ULL, ctypes.c_uint, _I, _P, _P],
     'pk_vocab_sample': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _ULL, _P, _I, _P, _P],
@@ -93,6 +94,7 @@ SIGNATURES = {
     'pk_topk_mask_keep': [_P, _I, _I, _P, _P, _P, _LL, _P, _P, _P, _P, _P],
     'pk_composite_mask': [_P, _P, _P, _P, _I, _I, _LL, _I, _P],
     'pk_critic_head': [_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _F, _ULL, _P, _P, _P],
+    'pk_critic_head_guided': [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _F, _ULL, _P, _P, _P],
     'pk_pack': [_P, _LL, _P, _I, _I, _I, _P, _LL, _I, _I, _P],
     'pk_scatter_rows': [_P, _LL, _P, _P, _LL, _I, _I, _P],
     'pk_colsum_parts': [_I],
@@ -759,6 +761,27 @@ def cfg_mix(x, nb, n_tot, n_prime, rows, nrows, scale, has_null, out, D):
     _check(rc, 'pk_cfg_mix')
 
 
+def _guidance_coef(coef, x, nb, n_tot, P, has_base, name):
+    """the table row of pk_guidance_mix / pk_critic_head_guided: contiguous f32 [(P + 1) * nb] on x's device, and x long enough for the
+    (P + has_base) * nb sequences the kernel reads (the C entry points cannot see either)"""
+    if coef is None or coef.dtype != torch.float32 or not coef.is_contiguous() or coef.device != x.device:
+        raise ValueError(f'{name}: coef must be a contiguous float32 tensor on {x.device}')
+    if 1 <= P <= 3:
+        if coef.numel() < (P + 1) * nb:
+            raise ValueError(f'{name}: coef holds {coef.numel()} values, P = {P} and nb = {nb} need {(P + 1) * nb}')
+        if x.shape[0] < (P + (1 if has_base else 0)) * nb * n_tot:
+            raise ValueError(f'{name}: x has {x.shape[0]} rows, {P} + {int(bool(has_base))} branches of {nb} x {n_tot} tokens need more')
+    return coef.data_ptr()
+
+
+def guidance_mix(x, nb, n_tot, n_prime, rows, nrows, coef, P, has_base, out, D):
+    """pk_guidance_mix: x ((P + has_base) * nb * n_tot, D) f32 laid out [cond_0 | .. | cond_{P-1} | base]; coef f32 [(P + 1) * nb] on the device
+    (blend weights a[k][b] in rows 0..P-1, the guidance scale g[b] in row P)"""
+    rc = load().pk_guidance_mix(ptr(x), x.stride(-2), nb, n_tot, n_prime, ptr(rows), nrows, _guidance_coef(coef, x, nb, n_tot, P, has_base, 'guidance_mix'),
+                                P, 1 if has_base else 0, ptr(out), out.stride(-2), 1 if out.dtype == torch.float32 else 0, D, stream(x))
+    _check(rc, 'pk_guidance_mix')
+
+
 def vocab_ntiles(V):
     return load().pk_vocab_ntiles(V)
 
@@ -945,6 +968,14 @@ def critic_head(x, w, b, D, nb, n_tot, n_prime, has_null, scale, u, noise_mult, 
     rc = load().pk_critic_head(ptr(x), x.stride(-2), f32p(w, 'critic head weight'), f32p(b, 'critic head bias'), D, nb, n_tot, n_prime, 1 if has_null else 0, scale,
                                ptr(u), noise_mult, seed & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), ptr(out), stream(x))
     _check(rc, 'pk_critic_head')
+
+
+def critic_head_guided(x, w, b, D, nb, n_tot, n_prime, coef, P, has_base, u, noise_mult, out, seed=0, seed_dev=None):
+    """pk_critic_head_guided: pk_critic_head with the table row of guidance_mix in place of scale / has_null"""
+    rc = load().pk_critic_head_guided(ptr(x), x.stride(-2), f32p(w, 'critic head weight'), f32p(b, 'critic head bias'), D, nb, n_tot, n_prime,
+                                      _guidance_coef(coef, x, nb, n_tot, P, has_base, 'critic_head_guided'), P, 1 if has_base else 0,
+                                      ptr(u), noise_mult, seed & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), ptr(out), stream(x))
+    _check(rc, 'pk_critic_head_guided')
 
 
 # ----------------------------------------------------------------------------- training-step kernels (csrc/train.hip, attn_train.hip)

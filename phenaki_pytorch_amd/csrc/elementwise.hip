@@ -257,6 +257,17 @@ __global__ __launch_bounds__(256) void cpb_input_kernel(const float* __restrict_
 // ---- critic score head (reference phenaki_pytorch.py:246-263, 523-545):
 //   s[r] = x[r] . w + b ;  out[b][i] = null + (cond - null) * scale  + noise_mult * (u - 0.5)
 // rows are laid out [cond sequences | null sequences]; prime positions are dropped (i >= n_prime).
+// one wave's x[r] . w + b: lane l takes columns 4 l + 256 j, pairwise within its four, then the wave sum (shared by the two head kernels)
+__device__ __forceinline__ float critic_row_dot(const float* __restrict__ xr, const float* __restrict__ w, float b, int D, int lane) {
+    float s = 0.f;
+    for (int c = lane * 4; c < D; c += 256) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + c);
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
+        s += (xv[0] * wv[0] + xv[1] * wv[1]) + (xv[2] * wv[2] + xv[3] * wv[3]);
+    }
+    return wave_sum(s) + b;
+}
+
 __global__ __launch_bounds__(256) void critic_head_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                           const float* __restrict__ bptr, int D, int nb, int n_tot, int n_prime, int has_null,
                                                           float scale, const float* __restrict__ u, float noise_mult,
@@ -268,22 +279,45 @@ __global__ __launch_bounds__(256) void critic_head_kernel(const float* __restric
     if (r >= nb * n) return;
     const int bi = r / n, i = r % n + n_prime;
     const float b = bptr ? bptr[0] : 0.f;
-    auto dot = [&](const float* xr) {
-        float s = 0.f;
-        for (int c = lane * 4; c < D; c += 256) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + c);
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
-            s += (xv[0] * wv[0] + xv[1] * wv[1]) + (xv[2] * wv[2] + xv[3] * wv[3]);
-        }
-        return wave_sum(s) + b;
-    };
-    float s = dot(x + ((size_t)bi * n_tot + i) * ldx);
+    float s = critic_row_dot(x + ((size_t)bi * n_tot + i) * ldx, w, b, D, lane);
     if (has_null) {
-        const float sn = dot(x + ((size_t)(nb + bi) * n_tot + i) * ldx);
+        const float sn = critic_row_dot(x + ((size_t)(nb + bi) * n_tot + i) * ldx, w, b, D, lane);
         s = sn + (s - sn) * scale;
     }
     if (u) s += noise_mult * (u[r] - 0.5f);
     else if (noise_mult != 0.f) {                           // FAST mode: the uniform draw of phenaki_pytorch.py:541 from the counter hash
+        const unsigned long long sd = seed + (seed_dev ? *seed_dev : 0ull);
+        s += noise_mult * (uniform24((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)r, 0xC817u) - 0.5f);
+    }
+    if (lane == 0) out[r] = s;
+}
+
+// critic_head_kernel with the guidance table of pk_guidance_mix in place of scale / has_null: rows [cond_0 | .. | cond_{P-1} | base],
+// coef[(P + 1) * nb] = a[k][b] in rows 0..P-1, g[b] in row P.  s = s_0 (P == 1) | sum_k a[k][b] s_k, k ascending; then base + (s - base) * g[b].
+__global__ __launch_bounds__(256) void critic_head_guided_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
+                                                                 const float* __restrict__ bptr, int D, int nb, int n_tot, int n_prime,
+                                                                 const float* __restrict__ coef, int P, int has_base,
+                                                                 const float* __restrict__ u, float noise_mult, unsigned long long seed,
+                                                                 const unsigned long long* __restrict__ seed_dev, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int n = n_tot - n_prime;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nb * n) return;
+    const int bi = r / n, i = r % n + n_prime;
+    const float b = bptr ? bptr[0] : 0.f;
+    float s = critic_row_dot(x + ((size_t)bi * n_tot + i) * ldx, w, b, D, lane);
+    if (P > 1) {
+        s = s * coef[bi];
+        for (int k = 1; k < P; ++k)
+            s = s + critic_row_dot(x + ((size_t)(k * nb + bi) * n_tot + i) * ldx, w, b, D, lane) * coef[k * nb + bi];
+    }
+    if (has_base) {
+        const float sn = critic_row_dot(x + ((size_t)(P * nb + bi) * n_tot + i) * ldx, w, b, D, lane);
+        const float scale = coef[P * nb + bi];
+        s = sn + (s - sn) * scale;
+    }
+    if (u) s += noise_mult * (u[r] - 0.5f);
+    else if (noise_mult != 0.f) {
         const unsigned long long sd = seed + (seed_dev ? *seed_dev : 0ull);
         s += noise_mult * (uniform24((uint32_t)sd, (uint32_t)(sd >> 32), (uint32_t)r, 0xC817u) - 0.5f);
     }
@@ -460,6 +494,19 @@ extern "C" int pk_critic_head(const float* x, int ldx, const float* w, const flo
     const int rows = nb * (n_tot - n_prime);
     hipLaunchKernelGGL(critic_head_kernel, dim3((rows + 3) / 4), dim3(256), 0, STREAM(stream), x, ldx, w, b, D, nb, n_tot, n_prime,
                        has_null, scale, u, noise_mult, seed, seed_dev, out);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_critic_head_guided(const float* x, int ldx, const float* w, const float* b, int D, int nb, int n_tot, int n_prime,
+                                     const float* coef, int P, int has_base, const float* u, float noise_mult, unsigned long long seed,
+                                     const unsigned long long* seed_dev, float* out, void* stream) {
+    if (!x || !w || !out || !coef || D <= 0 || nb <= 0 || n_tot <= n_prime || n_prime < 0) return PK_EINVAL;
+    if (P < 1 || P > 3 || (D & 3) || (!has_base && P == 1)) return PK_EINVAL;
+    if (ldx & 3) return PK_EALIGN;
+    const int rows = nb * (n_tot - n_prime);
+    hipLaunchKernelGGL(critic_head_guided_kernel, dim3((rows + 3) / 4), dim3(256), 0, STREAM(stream), x, ldx, w, b, D, nb, n_tot, n_prime,
+                       coef, P, has_base ? 1 : 0, u, noise_mult, seed, seed_dev, out);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

@@ -3,6 +3,8 @@
 //  pk_cfg_mix      : e = null + (cond - null) * scale on the 512-d trunk outputs.  Classifier-free guidance is
 //                    linear in the logits (phenaki_pytorch.py:155-161) and to_logits is linear, so mixing BEFORE
 //                    the vocab head gives the same logits with ONE 65 536-wide GEMM instead of two.
+//  pk_guidance_mix : the same mix for up to three weighted conditional branches and a null or negative-prompt base, with per-sample
+//                    scales read from a device table (Phenaki.sample's table path).
 //  pk_vocab_sample : logits = e @ W^T + b never touch HBM: the GEMM epilogue adds gumbel noise
 //                    (phenaki_pytorch.py:88-93), keeps per-row (best noisy value, index, raw logit) and, when no
 //                    critic is used, the online-softmax (max, sum exp) needed for 1 - softmax[pred] (:547-550);
@@ -32,6 +34,39 @@ __global__ __launch_bounds__(256) void cfg_mix_kernel(const float* __restrict__ 
         f32x4 v = *reinterpret_cast<const f32x4*>(x + ((size_t)b * n_tot + i) * ldx + c);
         if (has_null) {
             const f32x4 nv = *reinterpret_cast<const f32x4*>(x + ((size_t)(nb + b) * n_tot + i) * ldx + c);
+            v = nv + (v - nv) * scale;
+        }
+        if (out_f32) store4(reinterpret_cast<float*>(out) + (size_t)r * ldo + c, v);
+        else store4(reinterpret_cast<bf16*>(out) + (size_t)r * ldo + c, v);
+    }
+}
+
+// pk_guidance_mix: cfg_mix_kernel for P conditional branches and a base branch, x rows laid out [cond_0 | .. | cond_{P-1} | base] (nb sequences
+// each).  The weights and the scale come from a device table row coef[(P + 1) * nb]: rows 0..P-1 hold a[k][b], row P holds g[b].
+//   cbar = e_0 (P == 1, no multiply)  |  sum_k a[k][b] e_k, k ascending ;   out = base + (cbar - base) * g[b]   (has_base == 0: cbar)
+// The mix is cfg_mix_kernel's f32 expression: with P == 1 the two kernels agree bit for bit at equal scales.
+__global__ __launch_bounds__(256) void guidance_mix_kernel(const float* __restrict__ x, int ldx, int nb, int n_tot, int n_prime,
+                                                           const int* __restrict__ rows, int nrows, const float* __restrict__ coef, int P,
+                                                           int has_base, void* __restrict__ out, int ldo, int out_f32, int D) {
+    const int dv = D >> 2;
+    const int n = n_tot - n_prime;
+    const long total = (long)nrows * dv;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = (int)(idx % dv) * 4;
+        const int r = (int)(idx / dv);
+        const int lr = rows ? rows[r] : r;
+        const int b = lr / n, i = lr % n + n_prime;
+        f32x4 v = *reinterpret_cast<const f32x4*>(x + ((size_t)b * n_tot + i) * ldx + c);
+        if (P > 1) {
+            v = v * coef[b];
+            for (int k = 1; k < P; ++k) {
+                const f32x4 ev = *reinterpret_cast<const f32x4*>(x + ((size_t)(k * nb + b) * n_tot + i) * ldx + c);
+                v = v + ev * coef[k * nb + b];
+            }
+        }
+        if (has_base) {
+            const f32x4 nv = *reinterpret_cast<const f32x4*>(x + ((size_t)(P * nb + b) * n_tot + i) * ldx + c);
+            const float scale = coef[P * nb + b];
             v = nv + (v - nv) * scale;
         }
         if (out_f32) store4(reinterpret_cast<float*>(out) + (size_t)r * ldo + c, v);
@@ -1077,6 +1112,17 @@ extern "C" int pk_cfg_mix(const float* x, int ldx, int nb, int n_tot, int n_prim
     if ((D & 3) || (ldx & 3) || (ldo & 3)) return PK_EALIGN;
     hipLaunchKernelGGL(cfg_mix_kernel, dim3(nblocks((long)nrows * (D >> 2))), dim3(256), 0, STREAM(stream),
                        x, ldx, nb, n_tot, n_prime, rows, nrows, scale, has_null, out, ldo, out_is_f32, D);
+    PK_CHECK_LAUNCH();
+    return PK_OK;
+}
+
+extern "C" int pk_guidance_mix(const float* x, int ldx, int nb, int n_tot, int n_prime, const int* rows, int nrows, const float* coef, int P,
+                               int has_base, void* out, int ldo, int out_is_f32, int D, void* stream) {
+    if (!x || !out || !coef || nb <= 0 || n_tot <= n_prime || n_prime < 0 || nrows <= 0 || D <= 0) return PK_EINVAL;
+    if (P < 1 || P > 3 || (D & 3) || (!has_base && P == 1)) return PK_EINVAL;
+    if ((ldx & 3) || (ldo & 3)) return PK_EALIGN;
+    hipLaunchKernelGGL(guidance_mix_kernel, dim3(nblocks((long)nrows * (D >> 2))), dim3(256), 0, STREAM(stream),
+                       x, ldx, nb, n_tot, n_prime, rows, nrows, coef, P, has_base ? 1 : 0, out, ldo, out_is_f32, D);
     PK_CHECK_LAUNCH();
     return PK_OK;
 }

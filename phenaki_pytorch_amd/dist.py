@@ -65,6 +65,14 @@ def sample_sharded(phenaki, *, num_frames, texts=None, prime_frames=None, batch_
     rank, ws = world()
     lo, hi = shard_batch(n_items, rank, ws)
     assert hi > lo, f'rank {rank} received an empty shard: batch {n_items} < world size {ws}'
+    # the per-sample guidance arguments follow their samples: a sequence is sliced like `texts`, a value shared by the batch (a number, a
+    # str) goes to every rank as it is; guidance_schedule is per step, not per sample
+    per_sample = lambda v: v if v is None or isinstance(v, (str, int, float)) or getattr(v, 'ndim', 1) == 0 else _slice(v, lo, hi)
+    for name in ('cond_scale', 'negative_texts'):
+        if name in kwargs:
+            kwargs[name] = per_sample(kwargs[name])
+    if kwargs.get('blend') is not None:
+        kwargs['blend'] = [(per_sample(t), per_sample(w)) for t, w in kwargs['blend']]
     local = phenaki.sample(num_frames=num_frames, texts=_slice(texts, lo, hi), prime_frames=_slice(prime_frames, lo, hi),
                            batch_size=hi - lo, **kwargs)
     return all_gather_batch(local, n_items, force=_force_collective) if gather else local

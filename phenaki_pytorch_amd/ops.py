@@ -29,6 +29,9 @@ _lib.define('vocab_sample(Tensor x, Tensor w_packed, Tensor bias, Tensor? noise,
             'int seed, bool need_lse) -> Tensor(a!)')
 _lib.define('vocab_reduce(Tensor partials, Tensor? rows, Tensor? mask, Tensor? ids, Tensor(a!) pred, Tensor? scores, int vocab, bool need_lse) -> Tensor(a!)')
 _lib.define('lfq_decode(Tensor ids, Tensor project_out_weight, Tensor project_out_bias, Tensor(a!) out) -> Tensor(a!)')
+_lib.define('guidance_mix(Tensor x, Tensor coef, Tensor? rows, Tensor(a!) out, int nb, int n_tot, int n_prime, int branches, bool has_base) -> Tensor(a!)')
+_lib.define('critic_head_guided(Tensor x, Tensor w, Tensor? bias, Tensor coef, Tensor? noise, Tensor(a!) out, int nb, int n_tot, int n_prime, int branches, '
+            'bool has_base, float noise_mult, int seed) -> Tensor(a!)')
 
 
 def _gemm(x, w_packed, bias, res, out, dtype, act):
@@ -84,8 +87,20 @@ def _lfq_decode(ids, w, b, out):
     return out
 
 
+def _guidance_mix(x, coef, rows, out, nb, n_tot, n_prime, branches, has_base):
+    L.guidance_mix(x, nb, n_tot, n_prime, rows, out.shape[0], coef, branches, has_base, out, x.shape[1])
+    return out
+
+
+def _critic_head_guided(x, w, bias, coef, noise, out, nb, n_tot, n_prime, branches, has_base, noise_mult, seed):
+    L.critic_head_guided(x, w.reshape(-1), bias, x.shape[1], nb, n_tot, n_prime, coef, branches, has_base, noise, noise_mult, out, seed=seed)
+    return out
+
+
 for _name, _fn in (('gemm', _gemm), ('layernorm', _layernorm), ('peg', _peg), ('attn_prep', _attn_prep), ('attn_fwd', _attn_fwd),
-                   ('patch_embed', _patch_embed), ('vocab_sample', _vocab_sample), ('vocab_reduce', _vocab_reduce), ('lfq_decode', _lfq_decode)):
+                   ('patch_embed', _patch_embed), ('vocab_sample', _vocab_sample), ('vocab_reduce', _vocab_reduce), ('lfq_decode', _lfq_decode),
+                   ('guidance_mix', _guidance_mix), ('critic_head_guided', _critic_head_guided)):
     _lib.impl(_name, _fn, 'CUDA')                      # HIP devices dispatch under the CUDA key; no CPU kernel is registered
 
-OPS = ('gemm', 'layernorm', 'peg', 'attn_prep', 'attn_fwd', 'patch_embed', 'vocab_sample', 'vocab_reduce', 'lfq_decode')
+OPS = ('gemm', 'layernorm', 'peg', 'attn_prep', 'attn_fwd', 'patch_embed', 'vocab_sample', 'vocab_reduce', 'lfq_decode', 'guidance_mix',
+       'critic_head_guided')

@@ -141,6 +141,95 @@ def _cfg_masks(text_mask, nb, with_null):
     return torch.cat((tm, torch.zeros_like(tm)), dim=0).contiguous()
 
 
+# ---------------------------------------------------------------------------------------------- guided sampling: the table path
+# For sample b, step s and P conditional branches (1 <= P <= 3) with trunk outputs e_0 .. e_{P-1} and a base branch e_base (the null branch,
+# or the trunk on the negative prompt's context):
+#     cbar  = e_0 (P == 1)  |  sum_k a[k, b] e_k, k ascending, a[0, b] = 1 - sum_{k >= 1} a[k, b]
+#     mixed = e_base + (cbar - e_base) * g[s, b]
+#     g[s, b] = cond_scale[b]  |  1 + (cond_scale[b] - 1) * m[s] with a schedule m (float64 on the host, rounded once to f32)
+# (pk_guidance_mix on the trunk outputs, pk_critic_head_guided on the critic's scalar head outputs; DESIGN.md "Guided sampling").
+
+GUIDANCE_MAX_BRANCHES = 3
+
+
+def _is_scalar_scale(cond_scale):
+    """a Python number (or 0-d tensor): today's scalar path; a sequence / 1-D tensor / array: the table path"""
+    if torch.is_tensor(cond_scale):
+        return cond_scale.ndim == 0
+    return not (isinstance(cond_scale, (list, tuple)) or getattr(cond_scale, 'ndim', 0) > 0)
+
+
+def _floats(x, length, what):
+    """a number, or a sequence / 1-D tensor of `length` numbers -> list of `length` finite Python floats (ValueError otherwise)"""
+    if _is_scalar_scale(x):
+        vals = [float(x)] * length
+    else:
+        if getattr(x, 'ndim', 1) != 1:
+            raise ValueError(f'{what} must be a number or a 1-D sequence of {length} numbers')
+        vals = [float(v) for v in (x.tolist() if hasattr(x, 'tolist') else x)]
+        if len(vals) != length:
+            raise ValueError(f'{what} must hold {length} values, got {len(vals)}')
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f'{what} must be finite, got {vals}')
+    return vals
+
+
+def guidance_multipliers(guidance_schedule, steps):
+    """None | 'linear' (m[s] = (s + 1) / steps) | a sequence of `steps` finite floats -> None or the list m"""
+    if guidance_schedule is None:
+        return None
+    if isinstance(guidance_schedule, str):
+        if guidance_schedule != 'linear':
+            raise ValueError(f"guidance_schedule must be None, 'linear' or a sequence of {steps} floats, got {guidance_schedule!r}")
+        return [(s + 1) / steps for s in range(steps)]
+    if _is_scalar_scale(guidance_schedule):
+        raise ValueError(f"guidance_schedule must be None, 'linear' or a sequence of {steps} floats, got {guidance_schedule!r}")
+    return _floats(guidance_schedule, steps, f'guidance_schedule (one multiplier per step, steps = {steps})')
+
+
+def guidance_table(cond_scale, steps, multipliers=None, weights=()):
+    """the (steps, P + 1, B) float32 table of the table path, built in float64 and rounded once: rows 0..P-1 of a step hold the blend weights
+    a[k, b] (a[0, b] = 1 - sum_{k >= 1} a[k, b]; 1 when P == 1), row P the guidance scale g[s, b].  cond_scale: B floats; multipliers: None or
+    `steps` floats m[s]; weights: P - 1 lists of B floats (the blend branches, k = 1..P-1)."""
+    B, P = len(cond_scale), len(weights) + 1
+    t = torch.empty((steps, P + 1, B), dtype=torch.float64)
+    a0 = torch.ones((B,), dtype=torch.float64)
+    if P > 1:
+        w = torch.tensor(weights, dtype=torch.float64).reshape(P - 1, B)
+        t[:, 1:P] = w
+        a0 = 1. - w.sum(dim=0)
+    t[:, 0] = a0
+    cs = torch.tensor(cond_scale, dtype=torch.float64)
+    if multipliers is None:
+        t[:, P] = cs                                                      # the value itself, no arithmetic
+    else:
+        t[:, P] = 1. + (cs[None, :] - 1.) * torch.tensor(multipliers, dtype=torch.float64)[:, None]
+    return t.to(torch.float32)
+
+
+def guidance_contexts(conds, base=None):
+    """the contexts of the P conditional branches and the base branch as ONE batch: conds = [(context (B, L_k, d) f32, text mask (B, L_k) bool or
+    None = all True)], base = the same pair for a negative prompt, or None = the null branch (the first conditional context under an all-False
+    mask, as pk_cfg_mix's null half).  Every context is padded with zero rows to the longest length L; padded rows are masked out.
+    Returns (ctx (J * B, L, d) f32, mask (J * B, L) uint8), J = P + 1, laid out [cond_0 | .. | cond_{P-1} | base]."""
+    B, _, d = conds[0][0].shape
+    device = conds[0][0].device
+    branches = list(conds) + ([base] if base is not None else [])
+    for j, (c, m) in enumerate(branches):
+        if c.ndim != 3 or tuple(c.shape[::2]) != (B, d) or (m is not None and tuple(m.shape) != tuple(c.shape[:2])):
+            raise ValueError(f'guidance: branch {j} context is {tuple(c.shape)}, expected ({B}, L, {d}) with a (B, L) text mask')
+    Lmax = max(c.shape[1] for c, _ in branches)
+    J = len(conds) + 1
+    ctx = torch.zeros((J * B, Lmax, d), device=device, dtype=torch.float32)
+    tm = torch.zeros((J * B, Lmax), device=device, dtype=torch.uint8)
+    for j, (c, m) in enumerate(branches):
+        ctx[j * B:(j + 1) * B, :c.shape[1]] = c
+        tm[j * B:(j + 1) * B, :c.shape[1]] = 1 if m is None else m.to(torch.uint8)
+    if base is None:
+        ctx[(J - 1) * B:] = ctx[:B]
+    return ctx, tm
+
+
 class _TokenTrunk(PackedModule):
     """shared plumbing of MaskGit / TokenCritic: ids -> embeddings -> Transformer -> norm_out rows."""
 
@@ -236,7 +325,24 @@ class MaskGit(_TokenTrunk):
         return out.view(S, n, V)
 
     @torch.no_grad()
-    def forward_with_cond_scale(self, *args, cond_scale=3, **kwargs):
+    def forward_with_cond_scale(self, *args, cond_scale=3, negative_context=None, negative_text_mask=None, **kwargs):
+        """phenaki_pytorch.py:149-161.  A (B,) cond_scale, or negative_context (B, L, d) [negative_text_mask (B, L) bool] in place of the null
+        branch, takes the table path: logits of base + (cond - base) * cond_scale[b] (pk_guidance_mix on the trunk outputs)."""
+        if exists(negative_context) or not _is_scalar_scale(cond_scale):
+            kwargs = dict(kwargs)
+            x, vps = self._prepare(args[0], kwargs.get('text_mask'), kwargs.pop('video_patch_shape', None))
+            b, n = x.shape
+            context, video_mask = kwargs.get('context'), kwargs.get('video_mask')
+            if self.unconditional or not exists(context):
+                raise ValueError('forward_with_cond_scale: a per-sample cond_scale / negative_context needs a conditional MaskGit and a context')
+            table = guidance_table(_floats(cond_scale, b, 'cond_scale'), 1)[0]
+            ctx_r, tm_r = guidance_contexts([(context.float(), kwargs.get('text_mask'))],
+                                            (negative_context.float(), negative_text_mask) if exists(negative_context) else None)
+            e = self.embeds(x, replicas=2, video_patch_shape=vps, context=ctx_r, text_mask=tm_r,
+                            video_mask=None if video_mask is None else torch.cat((video_mask, video_mask), dim=0))
+            mixed = torch.empty((b * n, self.dim), device=x.device, dtype=L.tdtype(compute_dtype_of(self)))
+            L.guidance_mix(e, b, n, 0, None, b * n, table.to(x.device), 1, True, mixed, self.dim)
+            return self._logits(mixed, b * n, b, n)
         if cond_scale == 1:
             return self.forward(*args, cond_drop_prob=0., **kwargs)
         x = args[0]
@@ -330,10 +436,26 @@ class TokenCritic(_TokenTrunk):
         return x.reshape(x.shape[0], -1), vps
 
     @torch.no_grad()
-    def forward_with_cond_scale(self, *args, cond_scale=3, **kwargs):
+    def forward_with_cond_scale(self, *args, cond_scale=3, negative_context=None, negative_text_mask=None, **kwargs):
+        """phenaki_pytorch.py:251-263; a (B,) cond_scale or a negative_context mixes the head's scores as MaskGit.forward_with_cond_scale
+        mixes the trunk outputs (pk_critic_head_guided).  A critic without cross-attention never sees the text: plain scores."""
         kwargs = dict(kwargs)
         x, vps = self._flatten(args[0], kwargs.pop('video_patch_shape', None))
         context = kwargs.get('context')
+        if exists(negative_context) or not _is_scalar_scale(cond_scale):
+            b, n = x.shape
+            table = guidance_table(_floats(cond_scale, b, 'cond_scale'), 1)[0]
+            video_mask = kwargs.get('video_mask')
+            if not (self.has_cross_attn and exists(context)):
+                return self._scores(x, vps, context, kwargs.get('text_mask'), video_mask, 1., False)
+            ctx_r, tm_r = guidance_contexts([(context.float(), kwargs.get('text_mask'))],
+                                            (negative_context.float(), negative_text_mask) if exists(negative_context) else None)
+            e = self.embeds(x, replicas=2, video_patch_shape=vps, context=ctx_r, text_mask=tm_r,
+                            video_mask=None if video_mask is None else torch.cat((video_mask, video_mask), dim=0))
+            w, bias = self.head()
+            out = torch.empty((b, n), device=x.device, dtype=torch.float32)
+            L.critic_head_guided(e, w, bias, e.shape[1], b, n, 0, table.to(x.device), 1, True, None, 0., out)
+            return out
         with_null = cond_scale != 1 and exists(context)      # without context both passes are identical
         return self._scores(x, vps, context, kwargs.get('text_mask'), kwargs.get('video_mask'), cond_scale, with_null)
 
@@ -454,9 +576,10 @@ class Phenaki(PackedModule):
     def set_compute_dtype(self, name):
         return set_compute_dtype(self, name)
 
-    def sample_images(self, *, texts=None, batch_size=1, cond_scale=3., starting_temperature=0.9, noise_K=1.):
+    def sample_images(self, *, texts=None, batch_size=1, cond_scale=3., starting_temperature=0.9, noise_K=1., **guidance_kwargs):
+        """guidance_kwargs: sample's guidance_schedule / negative_texts / blend"""
         video = self.sample(texts=texts, num_frames=1, cond_scale=cond_scale, starting_temperature=starting_temperature,
-                            noise_K=noise_K)
+                            noise_K=noise_K, **guidance_kwargs)
         return video.squeeze(2)
 
     def forward(self, *args, **kwargs):
@@ -692,6 +815,8 @@ class Phenaki(PackedModule):
         seed_base = st['seed_base'] if seed_dev is None else 0          # graph mode: the base seed lives in *seed_dev
         M64 = 0xFFFFFFFFFFFFFFFF
         with_null, c_null = st['with_null'], st['c_null']
+        guided = st.get('guided')                                       # the table path (sample's guidance arguments): dict(P, J, critic_text), else None
+        c_guided = guided is not None and guided['critic_text']         # ... a critic that never sees the text keeps pk_critic_head
         need_lse = not exists(critic)
         mg_cache, cr_cache = {}, {}
         w_logits = linear_weight(mg.to_logits, dt)
@@ -726,9 +851,15 @@ class Phenaki(PackedModule):
             if trace is not None:
                 rec = dict(step=step, masked_ids=ids.clone(), mask=mask.bool().clone(), prime_ids=st['prime_ids'])
 
-            e = mg.embeds(ids, replicas=2 if with_null else 1, ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
-                          context=st['ctx_r'], text_mask=st['tm_r'], kv_cache=mg_cache)
-            L.cfg_mix(e, B, n_tot, npr, rows, M, float(st['cond_scale']), with_null, mixed, D)
+            if guided is not None:
+                # the table path: J = P + 1 branches [cond_0 | .. | cond_{P-1} | base] as one batch, mixed with this step's table row
+                e = mg.embeds(ids, replicas=guided['J'], ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
+                              context=st['ctx_r'], text_mask=st['tm_r'], kv_cache=mg_cache)
+                L.guidance_mix(e, B, n_tot, npr, rows, M, st['table'][step], guided['P'], True, mixed, D)
+            else:
+                e = mg.embeds(ids, replicas=2 if with_null else 1, ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
+                              context=st['ctx_r'], text_mask=st['tm_r'], kv_cache=mg_cache)
+                L.cfg_mix(e, B, n_tot, npr, rows, M, float(st['cond_scale']), with_null, mixed, D)
 
             temperature = st['starting_temperature'] * (steps_til_x0 / steps)
             U = noise_fn('gumbel', step, (B, n, V)) if noise_fn is not None else None
@@ -746,7 +877,7 @@ class Phenaki(PackedModule):
 
             if not is_last_step:
                 if exists(critic):
-                    ce = critic.embeds(ids, replicas=2 if c_null else 1, ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
+                    ce = critic.embeds(ids, replicas=guided['J'] if c_guided else (2 if c_null else 1), ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
                                        context=st['c_ctx_r'], text_mask=st['c_tm_r'], kv_cache=cr_cache)
                     if self.critic_noise_anneal_schedule == 'fixed':
                         noise_multiplier = 1.
@@ -758,9 +889,14 @@ class Phenaki(PackedModule):
                         raise ValueError('invalid critic noise anneal schedule name')
                     u = noise_fn('critic', step, (B, n)).contiguous() if noise_fn is not None else None
                     w, bias = critic.head()
-                    L.critic_head(ce, w, bias, ce.shape[1], B, n_tot, npr, c_null, float(st['cond_scale']), u,
-                                  float(st['noise_K'] * noise_multiplier), nxt,
-                                  seed=(seed_base + (2 * step + 1) * 0xD6E8FEB86659FD93) & M64, seed_dev=seed_dev)
+                    if c_guided:
+                        L.critic_head_guided(ce, w, bias, ce.shape[1], B, n_tot, npr, st['table'][step], guided['P'], True, u,
+                                             float(st['noise_K'] * noise_multiplier), nxt,
+                                             seed=(seed_base + (2 * step + 1) * 0xD6E8FEB86659FD93) & M64, seed_dev=seed_dev)
+                    else:
+                        L.critic_head(ce, w, bias, ce.shape[1], B, n_tot, npr, c_null, float(st['cond_scale']), u,
+                                      float(st['noise_K'] * noise_multiplier), nxt,
+                                      seed=(seed_base + (2 * step + 1) * 0xD6E8FEB86659FD93) & M64, seed_dev=seed_dev)
                 have_scores = True
                 if rec is not None:
                     rec['scores'] = nxt.clone()
@@ -794,11 +930,52 @@ class Phenaki(PackedModule):
             st['ids'].copy_(known_ids)
             st['known'].copy_(known)
 
+    def _guidance_plan(self, texts, cond_scale, guidance_schedule, negative_texts, blend):
+        """sample()'s guidance arguments, checked on the host (every ValueError of the table path, before anything is encoded or launched).
+        None: the scalar path (a Python-number cond_scale and no other guidance argument).  Else dict(B, table (steps, P + 1, B) f32 on the
+        host, P, blend_texts [str | list of B str], negative_texts None | str | list of B str)."""
+        if _is_scalar_scale(cond_scale) and guidance_schedule is None and negative_texts is None and blend is None:
+            return None
+        if texts is None or self.unconditional:
+            raise ValueError('sample: per-sample cond_scale / guidance_schedule / negative_texts / blend need texts and a conditional MaskGit')
+        B = 1 if isinstance(texts, str) else len(texts)
+
+        def branch_texts(t, what):
+            if isinstance(t, str):
+                return t
+            if not isinstance(t, (list, tuple)) or not all(isinstance(s, str) for s in t) or len(t) != B:
+                raise ValueError(f'sample: {what} must be a str or a list of {B} strings')
+            return list(t)
+
+        cs = _floats(cond_scale, B, 'sample: cond_scale')
+        m = guidance_multipliers(guidance_schedule, self.steps)
+        blend = [] if blend is None else list(blend)
+        if len(blend) > GUIDANCE_MAX_BRANCHES - 1:
+            raise ValueError(f'sample: blend takes at most {GUIDANCE_MAX_BRANCHES - 1} (texts, weight) pairs, got {len(blend)}')
+        blend_texts, weights = [], []
+        for k, pair in enumerate(blend):
+            if not isinstance(pair, (list, tuple)) or len(pair) != 2:
+                raise ValueError(f'sample: blend[{k}] must be a (texts, weight) pair')
+            blend_texts.append(branch_texts(pair[0], f'blend[{k}] texts'))
+            weights.append(_floats(pair[1], B, f'sample: blend[{k}] weight'))
+        if negative_texts is not None:
+            negative_texts = branch_texts(negative_texts, 'negative_texts')
+        return dict(B=B, P=1 + len(blend_texts), table=guidance_table(cs, self.steps, m, weights), blend_texts=blend_texts,
+                    negative_texts=negative_texts)
+
+    def _encode_branch(self, branch_texts, B, device):
+        """(embeddings (B, L, d) f32, text mask (B, L) bool = any(embeds != 0)) of one branch's texts; a str is encoded once and shared"""
+        shared = isinstance(branch_texts, str)
+        emb = self.encode_texts([branch_texts] if shared else branch_texts, output_device=device).to(device).float()
+        if shared and B > 1:
+            emb = emb.expand(B, -1, -1)
+        return emb, torch.any(emb != 0, dim=-1)
+
     @eval_decorator
     @torch.no_grad()
     def sample(self, *, num_frames, texts=None, prime_frames=None, batch_size=1, cond_scale=3.,
                starting_temperature=0.9, noise_K=1., _noise_fn=None, _trace=None, _return_ids=False, _compact=None, _seed=None,
-               _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None):
+               _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None, guidance_schedule=None, negative_texts=None, blend=None):
         """phenaki_pytorch.py:418-560.  `_noise_fn(kind, step, shape)` (tests) injects the U[0,1) draws of the
         reference run ('gumbel' (B,n,V) and 'critic' (B,n), device f32 tensors); _noise_fn='torch': torch's device generator in the
         reference's order (a seeded reference run on the same GPU draws the same noise); without it the noise comes from the
@@ -816,11 +993,25 @@ class Phenaki(PackedModule):
         and range errors (known ids outside [0, num_tokens), a sample with nothing to generate) are ValueErrors raised before anything
         launches.  The free counts F_b are read from the device once per call: ONE host synchronisation that a plain call does not have.
         With enable_sample_graph the counts are part of the configuration key: another mask with the same counts replays, other counts
-        capture again."""
+        capture again.
+
+        Guidance.  `cond_scale`: a Python number (the scalar path: one scale for the batch and all steps, baked into pk_cfg_mix /
+        pk_critic_head), or a sequence / 1-D tensor of B finite floats, one per sample.  `guidance_schedule`: None, 'linear'
+        (m[s] = (s + 1) / steps) or `steps` finite floats m[s]; the scale of step s is 1 + (cond_scale[b] - 1) m[s].  `negative_texts`: a str
+        shared by the batch or B strings; the guidance then points away from that text's trunk output instead of the null branch's.
+        `blend`: up to two (texts_k, weight_k) pairs, texts_k a str (shared) or B strings, weight_k a float or B floats: the conditional
+        output becomes (1 - sum_k weight_k) e(texts) + sum_k weight_k e(texts_k).  Any of these, or a non-scalar cond_scale, selects the
+        table path: all J = P + 1 branches (P conditional, then the base) run as one batch of J B sequences on contexts zero-padded to the
+        longest length (padded rows masked out), and pk_guidance_mix / pk_critic_head_guided read the weights and scales from a
+        (steps, P + 1, B) f32 device table built on the host once per call; the base branch always runs.  Wrong lengths, non-finite values,
+        more than two blend entries, a guidance argument without texts or on an unconditional MaskGit are ValueErrors raised before
+        anything launches.  With enable_sample_graph the table and the padded contexts are static inputs refilled per call, and the key
+        carries ('guided', P, has_negative, L) in place of the scale: calls that differ only in scales, schedule or weights replay one graph."""
         device = next(self.parameters()).device
         L.require_device(next(self.parameters()), 'Phenaki parameters')
         mg, critic = self.maskgit, self.critic
         dt = compute_dtype_of(mg)
+        plan = self._guidance_plan(texts, cond_scale, guidance_schedule, negative_texts, blend)
         known = free_counts = None
         if exists(known_ids) or exists(known_mask):
             if not (exists(known_ids) and exists(known_mask)):
@@ -872,6 +1063,15 @@ class Phenaki(PackedModule):
         # classifier-free guidance: the cond and null passes run as ONE batch of 2B sequences; context / masks of that batch
         # are laid out once per call (the null half = an all-False text mask, phenaki_pytorch.py:188-190)
         has_ctx = exists(text_embeds) and not mg.unconditional
+        guided = None
+        if plan is not None:
+            # the table path: every branch's context, zero-padded to the longest, laid out once per call as one (J B, L, d) batch
+            conds = [(text_embeds, text_mask)] + [self._encode_branch(t, B, device) for t in plan['blend_texts']]
+            base = self._encode_branch(plan['negative_texts'], B, device) if plan['negative_texts'] is not None else None
+            g_ctx, g_tm = guidance_contexts(conds, base)
+            guided = dict(P=plan['P'], J=plan['P'] + 1, has_negative=base is not None, L=g_ctx.shape[1],
+                          critic_text=exists(critic) and (isinstance(critic, SelfCritic) or critic.has_cross_attn))
+            cond_scale = 1.                                                    # not read on the table path (a text-blind critic: no mix)
         with_null = has_ctx and cond_scale != 1
         rep = lambda t: torch.cat((t, t), dim=0) if with_null else t
         c_has_ctx = exists(critic) and exists(text_embeds) and critic.has_cross_attn
@@ -893,6 +1093,10 @@ class Phenaki(PackedModule):
         key = (B, n, prime_token_length, prime_num_frames, tuple(patch_shape), None if text_embeds is None else tuple(text_embeds.shape),
                float(cond_scale), float(starting_temperature), float(noise_K), compact, dt, str(device), self.steps,
                self.critic_noise_anneal_schedule, None if known is None else tuple(free_counts))
+        if guided is not None:
+            # scales, schedule and weights live in the table (a static input): the key names the launch structure only
+            key = key[:5] + (tuple(g_ctx.shape), ('guided', guided['P'], guided['has_negative'], guided['L'])) + key[7:]
+        self.__dict__['_pk_last_sample_key'] = key
         graphs = self.__dict__.setdefault('_pk_sample_graphs', {}) if use_graph else None
         entry = graphs.get(key) if use_graph else None
         # a captured graph holds raw pointers to the live parameters AND to the packed copies derived from them: any change of a
@@ -903,7 +1107,11 @@ class Phenaki(PackedModule):
             entry = None
         if entry is not None:
             st = entry['st']
-            if has_ctx or c_has_ctx:
+            if guided is not None:
+                st['ctx_r'].copy_(g_ctx)
+                st['tm_r'].copy_(g_tm)
+                st['table'].copy_(plan['table'])
+            elif has_ctx or c_has_ctx:
                 entry['text_embeds'].copy_(text_embeds)
                 entry['tm'].copy_(text_mask)
                 # the CFG layouts are views/derived copies of the static inputs: rebuild them in place
@@ -929,6 +1137,11 @@ class Phenaki(PackedModule):
                   noise_fn=_noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base, seed_dev=None, with_null=with_null, c_null=c_null,
                   ctx_r=rep(text_embeds).contiguous() if has_ctx else None, tm_r=_cfg_masks(text_mask, B, with_null) if has_ctx else None,
                   c_ctx_r=crep(text_embeds).contiguous() if c_has_ctx else None, c_tm_r=_cfg_masks(text_mask, B, c_null) if c_has_ctx else None)
+        if guided is not None:
+            # g_ctx / g_tm were built for this call (nobody else holds them): with a graph they and the table become its static inputs
+            c_text = guided['critic_text']
+            st.update(guided=guided, table=plan['table'].to(device), ctx_r=g_ctx, tm_r=g_tm, c_ctx_r=g_ctx if c_text else None,
+                      c_tm_r=g_tm if c_text else None)
         if known is not None:
             ks, offs, totals = infill_schedule(free_counts, self.steps)
             st.update(ks=ks, totals=totals, known=torch.empty_like(known), ks_dev=torch.tensor(ks, dtype=torch.int32, device=device),
@@ -1004,8 +1217,9 @@ class Phenaki(PackedModule):
         return (mixed, *out[1:]) if isinstance(out, tuple) else mixed
 
 
-def make_video(phenaki: Phenaki, texts: List[str], num_frames, prime_lengths):
-    """phenaki_pytorch.py:691-714 : autoregressive scene chaining with K primed frames."""
+def make_video(phenaki: Phenaki, texts: List[str], num_frames, prime_lengths, **sample_kwargs):
+    """phenaki_pytorch.py:691-714 : autoregressive scene chaining with K primed frames.  sample_kwargs (cond_scale, guidance_schedule,
+    negative_texts, blend, ...) go to every scene's `sample`."""
     num_scenes = len(texts)
     num_frames = cast_tuple(num_frames, num_scenes)
     prime_lengths = cast_tuple(prime_lengths, num_scenes - 1)
@@ -1013,7 +1227,7 @@ def make_video(phenaki: Phenaki, texts: List[str], num_frames, prime_lengths):
     video_prime = None
     scenes = []
     for text, scene_num_frames, next_scene_prime_length in zip(texts, num_frames, prime_lengths):
-        video = phenaki.sample(texts=text, prime_frames=video_prime, num_frames=scene_num_frames)
+        video = phenaki.sample(texts=text, prime_frames=video_prime, num_frames=scene_num_frames, **sample_kwargs)
         scenes.append(video)
         video_prime = video[:, :, -next_scene_prime_length:]
     return torch.cat(scenes, dim=2), scenes
