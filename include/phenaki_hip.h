@@ -727,6 +727,19 @@ int pk_gemm_ex_form(int dtype, int a_is_f32, const void* A, int lda, const void*
 int pk_set_gemm_hot_forms(int on);
 int pk_get_gemm_hot_forms();
 
+/* A-resident form of the FF1 call (csrc/gemm_resident.hpp): a pk_gemm_ex call that is exactly form 4 (FF1) with K = 512 and variant 0
+ * (automatic, resolving to 24) runs ff1_resident_kernel -- a 128-row panel of A resident in LDS, W streamed to registers -- inside a measured window
+ * of M; the bf16 output is bit-identical to the tiled kernel's.  pk_gemm_ex_form still reports 4.
+ *   pk_set_ff1_resident:          0 the tiled kernel; 1 inside the window (default, or the environment's PK_FF1_RESIDENT); 2 at every M.  Read on the
+ *                                 host at every launch, so a captured graph keeps the kernel it was captured with.
+ *   pk_set_ff1_resident_workers:  tests only: n > 0 workgroups per panel and the resident kernel for every form-4 call at K = 512 (any M, any
+ *                                 variant argument); 0 (default, or PK_FF1_RESIDENT_WORKERS) restores the rule above.
+ *   pk_get_ff1_resident_launches: resident launches of this process so far. */
+int pk_set_ff1_resident(int mode);
+int pk_get_ff1_resident();
+int pk_set_ff1_resident_workers(int n);
+int pk_get_ff1_resident_launches();
+
 #ifdef __cplusplus
 }
 #endif

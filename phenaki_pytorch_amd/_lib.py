@@ -160,13 +160,18 @@ SIGNATURES = {
     'pk_gemm_ex_form': [_I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _I],
     'pk_set_gemm_hot_forms': [_I],
     'pk_get_gemm_hot_forms': [],
+    'pk_set_ff1_resident': [_I],
+    'pk_get_ff1_resident': [],
+    'pk_set_ff1_resident_workers': [_I],
+    'pk_get_ff1_resident_launches': [],
 }
 
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
 
 _lib = None
 _AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy', 'pk_gemm_epilogue_form', 'pk_gemm_ex_form', 'pk_set_gemm_hot_forms', 'pk_get_gemm_hot_forms',
-                'pk_vocab_ce_reg', 'pk_ce_grad_slab_reg', 'pk_vocab_weight_mean', 'pk_vocab_weight_mean_words')
+                'pk_vocab_ce_reg', 'pk_ce_grad_slab_reg', 'pk_vocab_weight_mean', 'pk_vocab_weight_mean_words',
+                'pk_set_ff1_resident', 'pk_get_ff1_resident', 'pk_set_ff1_resident_workers', 'pk_get_ff1_resident_launches')
 
 
 def load():
@@ -292,6 +297,26 @@ def set_gemm_hot_forms(on):
 
 def get_gemm_hot_forms():
     return load().pk_get_gemm_hot_forms()
+
+
+def set_ff1_resident(mode):
+    """A-resident form of the FF1 call (csrc/gemm_resident.hpp): 0 the tiled kernel, 1 inside the measured row window, 2 at every M; read at every
+    launch (a captured graph keeps the kernel it was captured with)"""
+    _check(load().pk_set_ff1_resident(int(mode)), 'pk_set_ff1_resident')
+
+
+def get_ff1_resident():
+    return load().pk_get_ff1_resident()
+
+
+def set_ff1_resident_workers(n):
+    """tests only: n > 0 workers per panel and the resident kernel for every FF1-form call at K = 512; 0: back to the dispatch rule"""
+    _check(load().pk_set_ff1_resident_workers(int(n)), 'pk_set_ff1_resident_workers')
+
+
+def ff1_resident_launches():
+    """resident launches of this process so far"""
+    return load().pk_get_ff1_resident_launches()
 
 
 def gemm_epilogue_form(dtype, variant, *, ln_kind=0, vec_ok=1, act=ACT_NONE, out_is_f32=1, bias=0, res=0, C2=0, stats_out=0, scatter=0,

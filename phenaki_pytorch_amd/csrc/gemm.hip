@@ -323,6 +323,10 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[TM][TN], int M,
     else gemm_epilogue_vec<T, TM, TN, WN, LNF, CpOff>(acc, M, N, e, m0, n0, rsum, rsq, K);
 }
 
+}  // namespace pk
+#include "gemm_resident.hpp"                             // ff1_resident_kernel: the A-resident form of the FF1 call (needs GemmEpilogue)
+namespace pk {
+
 template <typename T, typename TA, int TM, int TN>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmOperands p, const GemmEpilogue e) {
     using Tile = GemmTile<T, TA, TM, TN>;
@@ -624,6 +628,65 @@ static int& hot_forms_word() {
 extern "C" int pk_set_gemm_hot_forms(int on) { hot_forms_word() = on ? 1 : 0; return PK_OK; }
 extern "C" int pk_get_gemm_hot_forms() { return hot_forms_word(); }
 
+// ---- the A-resident form of the FF1 call (gemm_resident.hpp): the switch, the row window and the launch
+// PK_FF1_RESIDENT / pk_set_ff1_resident: 0 = the tiled kernel always; 1 (default) = the resident kernel where the call is exactly the FF1 form
+// (EPI_FF1) at K = 512, the main loop was left to the automatic choice (an explicit variant 24 stays the tiled loop: tools/gemm_bench.py,
+// the parity tests) and M lies inside the measured window below; 2 = the same without the window (probing other M).
+// PK_FF1_RESIDENT_WORKERS / pk_set_ff1_resident_workers(n > 0): tests only -- n workers per panel instead of n_cu / panels, and the
+// resident kernel for every EPI_FF1 call at K = 512 whatever its M or variant argument, so small shapes reach every path of the work split.
+static int& ff1_resident_word() {
+    static int v = [] { const char* e_ = getenv("PK_FF1_RESIDENT"); const int x = e_ ? atoi(e_) : 1; return x < 0 || x > 2 ? 1 : x; }();
+    return v;
+}
+static int& ff1_resident_workers_word() {
+    static int v = [] { const char* e_ = getenv("PK_FF1_RESIDENT_WORKERS"); const int x = e_ ? atoi(e_) : 0; return x > 0 ? x : 0; }();
+    return v;
+}
+static int& ff1_resident_launch_count() { static int n = 0; return n; }
+extern "C" int pk_set_ff1_resident(int mode) { if (mode < 0 || mode > 2) return PK_EINVAL; ff1_resident_word() = mode; return PK_OK; }
+extern "C" int pk_get_ff1_resident() { return ff1_resident_word(); }
+extern "C" int pk_set_ff1_resident_workers(int n) { if (n < 0 || n > 4096) return PK_EINVAL; ff1_resident_workers_word() = n; return PK_OK; }
+// resident launches of this process so far (wraps at 2^31); the dispatch report of tests/test_ff1_resident_gpu.py and tools/ff1_resident_ab.py
+extern "C" int pk_get_ff1_resident_launches() { return ff1_resident_launch_count(); }
+
+// the window, from profiles/ff1_resident.txt (MI355X, 256 CUs): the row counts at which the resident kernel met the keep rule -- 36 panels x 7
+// workers and 72 panels x 3, every worker with at most one left-over sub-block.  Measured and left out: 2304, 3584, 4096, 6144 (slower: 2 to 6
+// left-over sub-blocks per worker, each a W slice per wave for one MFMA per k-chunk), 3072 (within noise).
+static bool ff1_resident_window(int M) { return M == 4608 || M == 9216; }
+
+static int gemm_n_cu() {                                  // compute units of the current device (256 when the query fails)
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cus[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+
+// workers per panel of the resident launch this call gets, 0: the tiled path.  `form` is the call's epilogue form, `requested` the variant argument
+static int ff1_resident_workers(int form, int requested, int M, int K) {
+    if (form != EPI_FF1 || K != 64 * FR_NT || !ff1_resident_word()) return 0;
+    const int forced = ff1_resident_workers_word();
+    if (forced) return forced;
+    if (requested != 0) return 0;
+    if (ff1_resident_word() == 1 && !ff1_resident_window(M)) return 0;
+    const int w = gemm_n_cu() / ((M + 127) / 128);
+    return w < 1 ? 1 : w;
+}
+
+static int launch_ff1_resident(const GemmOperands& p, const GemmEpilogue& e, int workers, hipStream_t s) {
+    static LdsOptIn lds;
+    if (lds.raise(reinterpret_cast<const void*>(&ff1_resident_kernel), FR_SMEM) != PK_OK) return PK_ELAUNCH;
+    const long units = (long)((p.M + 127) / 128) * workers;
+    hipLaunchKernelGGL(ff1_resident_kernel, dim3((unsigned)(8 * ((units + 7) / 8))), dim3(512), FR_SMEM, s, p, e, workers);
+    PK_CHECK_LAUNCH();
+    ff1_resident_launch_count() = (ff1_resident_launch_count() + 1) & 0x7fffffff;
+    return PK_OK;
+}
+
 // the epilogue form (EPI_*) of a launch from the fields the launch itself sees: dtype and the resolved main-loop variant, ln_kind (0 no
 // LayerNorm fold, 1 in-loop statistics, 2 handed-over statistics), GemmEpilogue's vec_ok / act / out_f32 / pol / pol_res / dup_rows and
 // which of its optional operands are set.  A form only where the call IS that form; everything else 0, the generic epilogue.  Pure:
@@ -681,6 +744,7 @@ static int gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const void* 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 
     const bool dma_ok = dma_possible(dtype, a_is_f32, N, K, lda, ldw, a_nrows);
+    const int requested = variant;
     if (variant >= 100) { p.plain_map = 1; variant -= 100; }
     if (variant == 0) variant = auto_variant(dtype, a_is_f32, M, N, K, lda, ldw, a_nrows);
     if (variant >= 3 && !dma_ok) return PK_EINVAL;
@@ -691,6 +755,7 @@ static int gemm_ex(int dtype, int a_is_f32, const void* A, int lda, const void* 
         // LayerNorm-folded GEMM: LDS-DMA main loop only (the statistics come from its A fragments), vector epilogue, 64x64 / 128x128 tiles
         if (!dma_ok || !v || !al16(ln_s) || !al16(ln_t) || a_rows) return PK_EINVAL;
         if (form_only) { *form_only = form; return PK_OK; }
+        if (const int rw = ff1_resident_workers(form, requested, M, K)) return launch_ff1_resident(p, e, rw, s);
         if (form == EPI_FF1) return launch_dma<bf16, 4, 2, 2, 2, 4, 128, 0, 2, EPI_FF1>(p, e, a_nrows, s);
         // 128x128 wherever the automatic choice is a large tile (50: the 256x256 loop, which has no folded form)
         const bool big = variant == 24 || variant == 2 || variant == 9 || variant == 50;
