@@ -297,7 +297,9 @@ int pk_qkv_attn(int dtype, const void* xq, const void* xkv, int ld, const void* 
 /* Cross-attention against CACHED key / value images (the step-invariant text context, attention.py:142-182 with context) in ONE launch:
  * to_q (+ the folded LayerNorm, q_ln_s as in pk_qkv_project) + l2norm + softmax(q k^T (+ key mask)) v.  Kp / Vt are the images
  * pk_attn_prep wrote (same dtype) for nnull + n_kv <= 64 keys (nk_pad from pk_attn_pads); n % 64 == 0; kmask [S][n_kv] uint8 or NULL;
- * O bf16 (dtype 1) / f32 (dtype 2). */
+ * O bf16 (dtype 1) / f32 (dtype 2).  Kp / Vt are S * h * nk_pad * 64 elements each.  PRECONDITION: the Vt columns of the pad keys
+ * nnull + n_kv .. nk_pad - 1 hold finite values (pk_attn_prep zero-fills them; pk_qkv_project does NOT write them): the kernel gives
+ * them the weight 0 and 0 * NaN is NaN.  The pad rows of Kp may hold anything. */
 int pk_q_attn_cached(int dtype, const void* xq, int ld, const void* wq, int ldw, int S, int n, int h, int K, const float* q_scale, float scale,
                      const float* q_ln_s, const void* Kp, const void* Vt, int nk_pad, int n_kv, int nnull,
                      const unsigned char* kmask, void* O, int ldo, void* stream);

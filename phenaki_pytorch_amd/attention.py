@@ -664,7 +664,8 @@ class Attention(PackedModule):
         fill = cached is None                         # K^ / V^T are written by this call; else they are the step-invariant context images
         if fill:                                      # of the kv_cache and only the query side is projected / prepared again
             Kp = torch.empty((S * h * nk_pad * dh,), device=dev, dtype=td)
-            # V^T pad columns (keys >= n) are never written: the attention kernels mask them in the tail tile
+            # V^T pad columns (keys >= n) are never written by pk_qkv_project: pk_attn_fwd masks them in the tail tile.  pk_q_attn_cached does
+            # NOT (it needs them finite): only the images pk_attn_prep wrote below, pads zero-filled, go into the kv_cache it reads
             Vt = torch.empty((S * h * nk_pad * dh,), device=dev, dtype=td)
         else:
             Kp, Vt = cached

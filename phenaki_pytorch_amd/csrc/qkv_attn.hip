@@ -314,7 +314,10 @@ __global__ __launch_bounds__(256) void q_attn_cached_kernel(const QAttnCachedArg
     p.A = a.xq; p.W = a.wq; p.N = a.h * 64;
     qa_project_q<T>(p, M, m0, hh, a.K, a.q_scale, a.scale, a.q_ln_s, smem, Qs);   // its main loop ends with a barrier: the ring is dead
 
-    // K^ [key][64] -> Ks (slot ^ qa_ksw(key)), V^T [dim][keys] -> Vts (64-key rows of 128 B, slot ^ (dim & 7)); keys >= nk_pad: zeros
+    // K^ [key][64] -> Ks (slot ^ qa_ksw(key)), V^T [dim][keys] -> Vts (64-key rows of 128 B, slot ^ (dim & 7)); keys >= nk_pad: zeros.
+    // The V^T columns of the pad keys nk .. nk_pad - 1 are staged as they are: their softmax weight is exactly 0, so they must be FINITE
+    // (0 * NaN and 0 * Inf are NaN in the PV product) -- pk_attn_prep zero-fills them.  Zeroing them here was measured: 21.92 us against
+    // 21.77 us per launch in the sampling loop (profiles/qkv_parity.txt).  K^ pad rows may hold anything: their scores become -inf below.
     {
         const size_t sh = (size_t)s * a.h + hh;
         const int row = threadIdx.x >> 2, part = threadIdx.x & 3;          // 64 rows x 4 parts
@@ -455,7 +458,10 @@ extern "C" int pk_qkv_attn(int dtype, const void* xq, const void* xkv, int ld, c
 }
 
 // Cross-attention of S sequences of n tokens (n % 64 == 0) against cached K^ / V^T images of nk = nnull + n_kv <= 64 keys
-// (layouts of pk_attn_prep with nk_pad = pk_attn_pads(...); dtype 2: its pre-split bf16x3p images): O [S*n][ldo] (bf16 / f32) <-
+// (layouts of pk_attn_prep with nk_pad = pk_attn_pads(...); dtype 2: its pre-split bf16x3p images; S * h * nk_pad * 64 elements each.
+// PRECONDITION: the V^T columns of the pad keys nk .. nk_pad - 1 are finite -- pk_attn_prep writes zeros there; pk_qkv_project leaves
+// them unwritten, so its images must not be passed here unless the buffer was zeroed first.  K^ pad rows may hold anything):
+// O [S*n][ldo] (bf16 / f32) <-
 // softmax(l2norm(xq Wq^T) K^^T) V, heads merged.  kmask [S][n_kv] uint8 over the real keys or NULL; q_ln_s: LayerNorm folded into to_q
 // (xq = the un-normalised rows) or NULL.  Operand types per dtype as for pk_qkv_attn.
 extern "C" int pk_q_attn_cached(int dtype, const void* xq, int ld, const void* wq, int ldw, int S, int n, int h, int K, const float* q_scale,
