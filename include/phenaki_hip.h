@@ -742,6 +742,18 @@ int pk_get_ff1_resident();
 int pk_set_ff1_resident_workers(int n);
 int pk_get_ff1_resident_launches();
 
+/* A-resident form of the vocabulary head (csrc/sampler.hip vocab_resident_kernel): bf16, D = 512.  The same [tile][row] partials as the tiled kernel.
+ *   pk_set_vocab_resident:          0 the tiled kernel; 1 / 2 force the 8- / 12-wave build at M >= 1024; 3 (default, or the environment's
+ *                                   PK_VOCAB_RESIDENT) the measured rule: M >= 2048, 12 waves without the log-sum-exp state, 8 waves with it.  Read on the
+ *                                   host at every launch, so a captured graph keeps the kernel it was captured with.  PK_EINVAL outside 0..3.
+ *   pk_set_vocab_resident_workers:  tests only: n > 0 workgroups per XCD (grid 8 n) instead of 32; the kernel derives its work split from the grid.
+ *                                   0 restores the default.  PK_EINVAL outside 0..256.
+ *   pk_get_vocab_resident_launches: resident launches of this process so far. */
+int pk_set_vocab_resident(int mode);
+int pk_get_vocab_resident();
+int pk_set_vocab_resident_workers(int n);
+int pk_get_vocab_resident_launches();
+
 #ifdef __cplusplus
 }
 #endif

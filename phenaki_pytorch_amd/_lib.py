@@ -164,6 +164,10 @@ SIGNATURES = {
     'pk_get_ff1_resident': [],
     'pk_set_ff1_resident_workers': [_I],
     'pk_get_ff1_resident_launches': [],
+    'pk_set_vocab_resident': [_I],
+    'pk_get_vocab_resident': [],
+    'pk_set_vocab_resident_workers': [_I],
+    'pk_get_vocab_resident_launches': [],
 }
 
 _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride alignment)', -3: 'PK_ELAUNCH (HIP launch failed)'}
@@ -171,7 +175,8 @@ _ERR = {-1: 'PK_EINVAL (bad shape/size/flag)', -2: 'PK_EALIGN (pointer/stride al
 _lib = None
 _AB_OPTIONAL = ('pk_set_cache_policy', 'pk_get_cache_policy', 'pk_gemm_epilogue_form', 'pk_gemm_ex_form', 'pk_set_gemm_hot_forms', 'pk_get_gemm_hot_forms',
                 'pk_vocab_ce_reg', 'pk_ce_grad_slab_reg', 'pk_vocab_weight_mean', 'pk_vocab_weight_mean_words',
-                'pk_set_ff1_resident', 'pk_get_ff1_resident', 'pk_set_ff1_resident_workers', 'pk_get_ff1_resident_launches')
+                'pk_set_ff1_resident', 'pk_get_ff1_resident', 'pk_set_ff1_resident_workers', 'pk_get_ff1_resident_launches',
+                'pk_set_vocab_resident', 'pk_get_vocab_resident', 'pk_set_vocab_resident_workers', 'pk_get_vocab_resident_launches')
 
 
 def load():
@@ -317,6 +322,26 @@ def set_ff1_resident_workers(n):
 def ff1_resident_launches():
     """resident launches of this process so far"""
     return load().pk_get_ff1_resident_launches()
+
+
+def set_vocab_resident(mode):
+    """A-resident form of the vocabulary head (csrc/sampler.hip): 0 the tiled kernel, 1 / 2 force the 8- / 12-wave build (bf16, D = 512, M >= 1024),
+    3 the measured rule; read at every launch (a captured graph keeps the kernel it was captured with)"""
+    _check(load().pk_set_vocab_resident(int(mode)), 'pk_set_vocab_resident')
+
+
+def get_vocab_resident():
+    return load().pk_get_vocab_resident()
+
+
+def set_vocab_resident_workers(n):
+    """tests only: n > 0 workgroups per XCD in the resident vocabulary head (grid 8 n instead of 256); 0: the default"""
+    _check(load().pk_set_vocab_resident_workers(int(n)), 'pk_set_vocab_resident_workers')
+
+
+def vocab_resident_launches():
+    """resident vocabulary-head launches of this process so far"""
+    return load().pk_get_vocab_resident_launches()
 
 
 def gemm_epilogue_form(dtype, variant, *, ln_kind=0, vec_ok=1, act=ACT_NONE, out_is_f32=1, bias=0, res=0, C2=0, stats_out=0, scatter=0,

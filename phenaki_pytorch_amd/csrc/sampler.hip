@@ -1129,6 +1129,23 @@ extern "C" int pk_guidance_mix(const float* x, int ldx, int nb, int n_tot, int n
 
 extern "C" int pk_vocab_ntiles(int V) { return (V + 127) / 128; }
 
+// ---- the switches of the A-resident vocabulary head (vocab_resident_kernel), modelled on pk_set_ff1_resident (gemm.hip)
+// PK_VOCAB_RESIDENT / pk_set_vocab_resident: 0 = the tiled kernel, 1 / 2 = force the 8- / 12-wave build (bf16, D = 512, M >= 1024), 3 (default) = the
+// measured rule in vocab_sample_launch.  The environment gives the initial value; the word is read at every launch (a captured graph keeps its kernel).
+// pk_set_vocab_resident_workers(n > 0): tests only -- n workgroups per XCD (grid 8 n) instead of 32; the kernel derives its work split from gridDim.x,
+// so a 1 300-row case reaches the segments that need more than 4 096 rows at 32 workers.  0: the default grid.
+static int& vocab_resident_word() {
+    static int v = [] { const char* e_ = getenv("PK_VOCAB_RESIDENT"); const int x = e_ ? atoi(e_) : 3; return x < 0 || x > 3 ? 3 : x; }();
+    return v;
+}
+static int& vocab_resident_workers_word() { static int v = 0; return v; }
+static int& vocab_resident_launch_count() { static int n = 0; return n; }
+extern "C" int pk_set_vocab_resident(int mode) { if (mode < 0 || mode > 3) return PK_EINVAL; vocab_resident_word() = mode; return PK_OK; }
+extern "C" int pk_get_vocab_resident() { return vocab_resident_word(); }
+extern "C" int pk_set_vocab_resident_workers(int n) { if (n < 0 || n > 256) return PK_EINVAL; vocab_resident_workers_word() = n; return PK_OK; }
+// resident launches of this process so far (wraps at 2^31): the dispatch report of tests/test_vocab_parity_gpu.py
+extern "C" int pk_get_vocab_resident_launches() { return vocab_resident_launch_count(); }
+
 // workspace: 5 arrays of ntiles*M 4-byte words, passed as one buffer `partials` of 5*ntiles*M words
 static int vocab_sample_launch(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias,
                                int M, int V, int D, float temperature, const float* U, const int* rows,
@@ -1164,12 +1181,13 @@ static int vocab_sample_launch(int dtype, const void* A, int lda, const void* W,
     // twelve waves with a ring of 4 k-tiles (3 waves per SIMD, 153 VGPRs) win when the epilogue carries the noise hash (432 vs 451 us), eight
     // waves with a ring of 8 and double-buffered A fragments (2 per SIMD) when it carries the log-sum-exp state (the 12-wave build of that
     // variant spills); below ~2048 rows the panel swap and the start-up are no longer amortised (1152 rows: 146 vs 139 us tiled).
-    // PK_VOCAB_RESIDENT: 0 = the tiled kernel, 1 / 2 = force the 8- / 12-wave build, unset = the rule above.
-    static const int resident_env = [] { const char* v = getenv("PK_VOCAB_RESIDENT"); return v ? atoi(v) : 3; }();
+    // PK_VOCAB_RESIDENT / pk_set_vocab_resident: 0 = the tiled kernel, 1 / 2 = force the 8- / 12-wave build, 3 (unset) = the rule above.
+    const int resident_env = vocab_resident_word();
     if (dtype == 1 && resident_env && D == 64 * VR_NT && M >= (resident_env == 3 ? 2048 : 1024)) {
         const bool lse = e.need_lse != 0;
         const int vi = (parity ? 2 : 0) + (lse ? 1 : 0);
-        const dim3 rgrid(256);                                         // 8 XCDs x 32 CUs: one workgroup per CU
+        const int forced_workers = vocab_resident_workers_word();
+        const dim3 rgrid(forced_workers ? 8 * forced_workers : 256);   // 8 XCDs x 32 CUs: one workgroup per CU (tests: 8 x n)
 #define PK_VR(NWV, RNG, FA, TW, PAR, LS) do { \
             static pk::LdsOptIn lds; \
             if (lds.raise(reinterpret_cast<const void*>(&vocab_resident_kernel<NWV, RNG, FA, TW, PAR, LS>), VR_SMEM) != PK_OK) return PK_ELAUNCH; \
@@ -1183,6 +1201,7 @@ static int vocab_sample_launch(int dtype, const void* A, int lda, const void* W,
         }
 #undef PK_VR
         PK_CHECK_LAUNCH();
+        vocab_resident_launch_count() = (vocab_resident_launch_count() + 1) & 0x7fffffff;
         return PK_OK;
     }
 #define PK_VS(TT, PAR, LS) hipLaunchKernelGGL((vocab_sample_kernel<TT, PAR, LS>), grid, dim3(VocabTile<TT>::THREADS), VocabTile<TT>::SMEM, s, p, e)

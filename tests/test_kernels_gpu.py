@@ -616,10 +616,25 @@ def test_vocab_sample_fast_mode_matches_its_numpy_twin(L):
 
 @pytest.mark.parametrize('M,V', [(1100, 4136), (1024, 65536), (2500, 1024)])
 def test_vocab_head_resident_kernel(L, M, V):
-    """bf16, D = 512, M >= 1024 routes pk_vocab_sample to the A-resident persistent kernel (sampler.hip vocab_resident_kernel): rows that do not
-    fill the last 128-row panel, a vocabulary that does not fill its last tile / its XCD ranges unevenly (33 tiles over 8 XCDs), workers that
-    change row panels.  (1) PARITY noise from memory: gumbel-argmax ids outside near-ties, confidence scores; (2) cross entropy through the
-    log-sum-exp partials with the row indirection; (3) FAST noise against the numpy twin of the counter hash, seeded and deterministic."""
+    """bf16, D = 512 on the A-resident persistent kernel (sampler.hip vocab_resident_kernel), selected with pk_set_vocab_resident and held to the launch
+    counter: the 8-wave build at 1100 rows and the 12-wave build at 1024 rows are forced (the measured rule starts at 2048 rows, so these two shapes ran
+    the tiled kernel while the mode could only be set through the environment); 2500 rows run under the rule itself.  Rows that do not fill the last
+    128-row panel, a vocabulary that does not fill its last tile / its XCD ranges unevenly (33 tiles over 8 XCDs), workers that change row panels.
+    (1) PARITY noise from memory: gumbel-argmax ids outside near-ties, confidence scores; (2) cross entropy through the log-sum-exp partials with the
+    row indirection; (3) FAST noise against the numpy twin of the counter hash, seeded and deterministic.  Per-element parity of the same kernel:
+    tests/test_vocab_parity_gpu.py."""
+    mode = {1100: 1, 1024: 2, 2500: 3}[M]
+    saved, before = L.get_vocab_resident(), L.vocab_resident_launches()
+    L.set_vocab_resident(mode)
+    try:
+        _vocab_head_resident_body(L, M, V)
+    finally:
+        L.set_vocab_resident(saved)
+    want = 4 if M * V <= 5_000_000 else 1                                          # (1) one launch, (2) one, (3) two; the large vocabulary runs (2) only
+    assert L.vocab_resident_launches() - before == want, 'pk_vocab_sample did not take the resident kernel'
+
+
+def _vocab_head_resident_body(L, M, V):
     D = 512
     e = torch.randn(M, D, generator=g(60))
     W = torch.randn(V, D, generator=g(61)) / math.sqrt(D) * 3
