@@ -12,6 +12,7 @@ cross entropy without logits (pk_vocab_sample statistics + pk_vocab_ce) + the to
 """
 import math
 from functools import partial
+from collections import namedtuple
 from typing import List
 
 import torch
@@ -48,6 +49,32 @@ def prob_mask_like(shape, prob, device):
     elif prob == 0:
         return torch.zeros(shape, device=device, dtype=torch.bool)
     return torch.zeros(shape, device=device).float().uniform_(0, 1) < prob
+
+
+def default_text_mask(context, text_mask, device):
+    """no text mask with a context means all True"""
+    if exists(context) and not exists(text_mask):
+        return torch.ones(context.shape[:2], device=device, dtype=torch.bool)
+    return text_mask
+
+
+def cond_drop_text_mask(context, text_mask, cond_drop_prob, b, device, *, needs_context):
+    """the text mask of a forward call: the default one, then classifier-free-guidance dropout -- a prob_mask_like((b,), 1 - p) keep draw ANDed
+    into it, drawn only when the guard below holds and p > 0."""
+    # needs_context: False = MaskGit, which drops whenever a text mask exists (phenaki_pytorch.py:188-189); True = TokenCritic, only with a context (:286-287)
+    text_mask = default_text_mask(context, text_mask, device)
+    guard = exists(context) if needs_context else exists(text_mask)
+    if guard and exists(cond_drop_prob) and cond_drop_prob > 0:
+        text_mask = prob_mask_like((b,), 1 - cond_drop_prob, device=device)[:, None] & text_mask
+    return text_mask
+
+
+def critic_noise_multiplier(schedule, step, steps):
+    """the critic's noise scale at `step` as a fraction of noise_K (phenaki_pytorch.py:533-540)"""
+    multipliers = dict(fixed=1., decay=(steps - (step + 1)) / steps, increase=(step + 1) / steps)
+    if schedule not in multipliers:
+        raise ValueError('invalid critic noise anneal schedule name')
+    return multipliers[schedule]
 
 
 def mask_schedule(num_tokens, steps):
@@ -270,8 +297,36 @@ class _TokenTrunk(PackedModule):
                                     cross_attn_context_mask=_u8(text_mask) if ctx2 is not None else None,
                                     kv_cache=kv_cache, replicas=2 if shared else 1)
 
+    def _cfg_embeds(self, x, video_patch_shape, context, text_mask, video_mask, with_null=True):
+        """the scalar CFG layout: `embeds` of the 2b sequences [cond | null] -- context and masks doubled, the null half under an all-False text
+        mask -- for pk_cfg_mix / pk_critic_head with has_null; with_null False: the plain b sequences"""
+        if not with_null:
+            return self.embeds(x, video_patch_shape=video_patch_shape, context=context, text_mask=text_mask, video_mask=video_mask)
+        rep = lambda t: None if t is None else torch.cat((t, t), dim=0)
+        return self.embeds(x, replicas=2, video_patch_shape=video_patch_shape, context=rep(context), text_mask=rep(text_mask),
+                           video_mask=rep(video_mask), null_rows=x.shape[0])
+
+    def _guided_embeds(self, x, video_patch_shape, context, text_mask, video_mask, cond_scale, negative_context, negative_text_mask):
+        """the table layout with one conditional branch: `embeds` of the 2b sequences [cond | base] (base: the negative context, else the null
+        branch) and the (2, b) device table row [1 | cond_scale[b]] for pk_guidance_mix / pk_critic_head_guided"""
+        b = x.shape[0]
+        table = guidance_table(_floats(cond_scale, b, 'cond_scale'), 1)[0]
+        ctx_r, tm_r = guidance_contexts([(context.float(), text_mask)],
+                                        (negative_context.float(), negative_text_mask) if exists(negative_context) else None)
+        e = self.embeds(x, replicas=2, video_patch_shape=video_patch_shape, context=ctx_r, text_mask=tm_r,
+                        video_mask=None if video_mask is None else torch.cat((video_mask, video_mask), dim=0))
+        return e, table.to(x.device)
+
     def set_compute_dtype(self, name):
         return set_compute_dtype(self, name)
+
+
+def _critic_scores(critic, e, b, n, with_null=False, cond_scale=1.):
+    """(b, n) f32 scores of a critic's head on its trunk rows `e` (pk_critic_head: no noise; with_null mixes the [cond | null] halves)"""
+    w, bias = critic.head()
+    out = torch.empty((b, n), device=e.device, dtype=torch.float32)
+    L.critic_head(e, w, bias, e.shape[1], b, n, 0, with_null, float(cond_scale), None, 0., out)
+    return out
 
 
 class MaskGit(_TokenTrunk):
@@ -307,12 +362,11 @@ class MaskGit(_TokenTrunk):
         masks cover all S sequences; the LAST `null_rows` sequences get an all-False text mask (cond_drop_prob = 1,
         phenaki_pytorch.py:188-190) unless the caller already prepared a uint8 mask (sample())."""
         S = replicas * x.shape[0]
-        if exists(context) and not exists(text_mask):
-            text_mask = torch.ones(context.shape[:2], device=x.device, dtype=torch.bool)
+        text_mask = default_text_mask(context, text_mask, x.device)
         if exists(text_mask) and null_rows and text_mask.dtype != torch.uint8:
             text_mask = text_mask.clone()
             text_mask[S - null_rows:] = False
-        bias = self.continuous_pos_bias.spec(*video_patch_shape)       # matrix or relative-position table, as each attention launch can use
+        bias =self.continuous_pos_bias.spec(*video_patch_shape)       # matrix or relative-position table, as each attention launch can use
         return self._trunk(x, video_patch_shape, context=context, text_mask=text_mask, video_mask=video_mask,
                            attn_bias=bias, use_cross=not self.unconditional, kv_cache=kv_cache, replicas=replicas,
                            ids_prime=ids_prime)
@@ -328,34 +382,22 @@ class MaskGit(_TokenTrunk):
     def forward_with_cond_scale(self, *args, cond_scale=3, negative_context=None, negative_text_mask=None, **kwargs):
         """phenaki_pytorch.py:149-161.  A (B,) cond_scale, or negative_context (B, L, d) [negative_text_mask (B, L) bool] in place of the null
         branch, takes the table path: logits of base + (cond - base) * cond_scale[b] (pk_guidance_mix on the trunk outputs)."""
-        if exists(negative_context) or not _is_scalar_scale(cond_scale):
-            kwargs = dict(kwargs)
-            x, vps = self._prepare(args[0], kwargs.get('text_mask'), kwargs.pop('video_patch_shape', None))
-            b, n = x.shape
-            context, video_mask = kwargs.get('context'), kwargs.get('video_mask')
-            if self.unconditional or not exists(context):
-                raise ValueError('forward_with_cond_scale: a per-sample cond_scale / negative_context needs a conditional MaskGit and a context')
-            table = guidance_table(_floats(cond_scale, b, 'cond_scale'), 1)[0]
-            ctx_r, tm_r = guidance_contexts([(context.float(), kwargs.get('text_mask'))],
-                                            (negative_context.float(), negative_text_mask) if exists(negative_context) else None)
-            e = self.embeds(x, replicas=2, video_patch_shape=vps, context=ctx_r, text_mask=tm_r,
-                            video_mask=None if video_mask is None else torch.cat((video_mask, video_mask), dim=0))
-            mixed = torch.empty((b * n, self.dim), device=x.device, dtype=L.tdtype(compute_dtype_of(self)))
-            L.guidance_mix(e, b, n, 0, None, b * n, table.to(x.device), 1, True, mixed, self.dim)
-            return self._logits(mixed, b * n, b, n)
-        if cond_scale == 1:
+        guided = exists(negative_context) or not _is_scalar_scale(cond_scale)
+        if not guided and cond_scale == 1:
             return self.forward(*args, cond_drop_prob=0., **kwargs)
-        x = args[0]
         kwargs = dict(kwargs)
-        x, vps = self._prepare(x, kwargs.get('text_mask'), kwargs.pop('video_patch_shape', None))
+        x, vps = self._prepare(args[0], kwargs.get('text_mask'), kwargs.pop('video_patch_shape', None))
         b, n = x.shape
         context, text_mask, video_mask = kwargs.get('context'), kwargs.get('text_mask'), kwargs.get('video_mask')
-        rep = lambda t: None if t is None else torch.cat((t, t), dim=0)
-        e = self.embeds(x, replicas=2, video_patch_shape=vps, context=rep(context), text_mask=rep(text_mask),
-                        video_mask=rep(video_mask), null_rows=b)
-        dt = compute_dtype_of(self)
-        mixed = torch.empty((b * n, self.dim), device=x.device, dtype=L.tdtype(dt))
-        L.cfg_mix(e, b, n, 0, None, b * n, float(cond_scale), True, mixed, self.dim)
+        mixed = torch.empty((b * n, self.dim), device=x.device, dtype=L.tdtype(compute_dtype_of(self)))
+        if guided:
+            if self.unconditional or not exists(context):
+                raise ValueError('forward_with_cond_scale: a per-sample cond_scale / negative_context needs a conditional MaskGit and a context')
+            e, coef = self._guided_embeds(x, vps, context, text_mask, video_mask, cond_scale, negative_context, negative_text_mask)
+            L.guidance_mix(e, b, n, 0, None, b * n, coef, 1, True, mixed, self.dim)
+        else:
+            e = self._cfg_embeds(x, vps, context, text_mask, video_mask)
+            L.cfg_mix(e, b, n, 0, None, b * n, float(cond_scale), True, mixed, self.dim)
         return self._logits(mixed, b * n, b, n)
 
     def forward(self, x, cond_drop_prob=0., text_mask=None, video_mask=None, video_patch_shape=None,
@@ -377,11 +419,7 @@ class MaskGit(_TokenTrunk):
         b, n = x.shape
         context = kwargs.pop('context', None)
         assert not kwargs, f'unexpected arguments {sorted(kwargs)}'
-        if exists(context) and not exists(text_mask):
-            text_mask = torch.ones(context.shape[:2], device=x.device, dtype=torch.bool)
-        if cond_drop_prob > 0 and exists(text_mask):
-            keep_mask = prob_mask_like((b,), 1 - cond_drop_prob, device=x.device)
-            text_mask = keep_mask[:, None] & text_mask
+        text_mask = cond_drop_text_mask(context, text_mask, cond_drop_prob, b, x.device, needs_context=False)
         e = self.embeds(x, video_patch_shape=vps, context=context, text_mask=text_mask, video_mask=video_mask)
         if return_embeds:
             return e.view(b, n, self.dim)
@@ -406,8 +444,7 @@ class TokenCritic(_TokenTrunk):
     def embeds(self, x, *, video_patch_shape, context=None, text_mask=None, video_mask=None, null_rows=0, kv_cache=None,
                replicas=1, ids_prime=None):
         S = replicas * x.shape[0]
-        if exists(context) and not exists(text_mask):
-            text_mask = torch.ones(context.shape[:2], device=x.device, dtype=torch.bool)
+        text_mask = default_text_mask(context, text_mask, x.device)
         if exists(text_mask) and exists(context) and null_rows and text_mask.dtype != torch.uint8:
             text_mask = text_mask.clone()
             text_mask[S - null_rows:] = False
@@ -415,17 +452,8 @@ class TokenCritic(_TokenTrunk):
                            use_cross=self.has_cross_attn, kv_cache=kv_cache, replicas=replicas, ids_prime=ids_prime)
 
     def _scores(self, x, video_patch_shape, context, text_mask, video_mask, cond_scale, with_null):
-        b, n = x.shape
-        rep = lambda t: None if t is None else torch.cat((t, t), dim=0)
-        if with_null:
-            e = self.embeds(x, replicas=2, video_patch_shape=video_patch_shape, context=rep(context),
-                            text_mask=rep(text_mask), video_mask=rep(video_mask), null_rows=b)
-        else:
-            e = self.embeds(x, video_patch_shape=video_patch_shape, context=context, text_mask=text_mask, video_mask=video_mask)
-        w, bias = self.head()
-        out = torch.empty((b, n), device=x.device, dtype=torch.float32)
-        L.critic_head(e, w, bias, e.shape[1], b, n, 0, with_null, float(cond_scale), None, 0., out)
-        return out
+        e = self._cfg_embeds(x, video_patch_shape, context, text_mask, video_mask, with_null)
+        return _critic_scores(self, e, *x.shape, with_null, cond_scale)
 
     @staticmethod
     def _flatten(x, video_patch_shape):
@@ -441,23 +469,19 @@ class TokenCritic(_TokenTrunk):
         mixes the trunk outputs (pk_critic_head_guided).  A critic without cross-attention never sees the text: plain scores."""
         kwargs = dict(kwargs)
         x, vps = self._flatten(args[0], kwargs.pop('video_patch_shape', None))
-        context = kwargs.get('context')
+        context, text_mask, video_mask = kwargs.get('context'), kwargs.get('text_mask'), kwargs.get('video_mask')
         if exists(negative_context) or not _is_scalar_scale(cond_scale):
             b, n = x.shape
-            table = guidance_table(_floats(cond_scale, b, 'cond_scale'), 1)[0]
-            video_mask = kwargs.get('video_mask')
             if not (self.has_cross_attn and exists(context)):
-                return self._scores(x, vps, context, kwargs.get('text_mask'), video_mask, 1., False)
-            ctx_r, tm_r = guidance_contexts([(context.float(), kwargs.get('text_mask'))],
-                                            (negative_context.float(), negative_text_mask) if exists(negative_context) else None)
-            e = self.embeds(x, replicas=2, video_patch_shape=vps, context=ctx_r, text_mask=tm_r,
-                            video_mask=None if video_mask is None else torch.cat((video_mask, video_mask), dim=0))
+                _floats(cond_scale, b, 'cond_scale')                            # the argument is still checked
+                return self._scores(x, vps, context, text_mask, video_mask, 1., False)
+            e, coef = self._guided_embeds(x, vps, context, text_mask, video_mask, cond_scale, negative_context, negative_text_mask)
             w, bias = self.head()
             out = torch.empty((b, n), device=x.device, dtype=torch.float32)
-            L.critic_head_guided(e, w, bias, e.shape[1], b, n, 0, table.to(x.device), 1, True, None, 0., out)
+            L.critic_head_guided(e, w, bias, e.shape[1], b, n, 0, coef, 1, True, None, 0., out)
             return out
         with_null = cond_scale != 1 and exists(context)      # without context both passes are identical
-        return self._scores(x, vps, context, kwargs.get('text_mask'), kwargs.get('video_mask'), cond_scale, with_null)
+        return self._scores(x, vps, context, text_mask, video_mask, cond_scale, with_null)
 
     def forward(self, x, text_mask=None, cond_drop_prob=None, context=None, video_mask=None, video_patch_shape=None, **kwargs):
         """phenaki_pytorch.py:265-302; under grad mode with trainable parameters: with an autograd graph (train.py)"""
@@ -470,12 +494,7 @@ class TokenCritic(_TokenTrunk):
 
     def _forward_value(self, x, text_mask=None, cond_drop_prob=None, context=None, video_mask=None, video_patch_shape=None):
         x, vps = self._flatten(x, video_patch_shape)
-        b = x.shape[0]
-        if exists(context) and not exists(text_mask):
-            text_mask = torch.ones(context.shape[:2], device=x.device, dtype=torch.bool)
-        if exists(context) and exists(cond_drop_prob) and cond_drop_prob > 0:
-            keep_mask = prob_mask_like((b,), 1 - cond_drop_prob, device=x.device)
-            text_mask = keep_mask[:, None] & text_mask
+        text_mask = cond_drop_text_mask(context, text_mask, cond_drop_prob, x.shape[0], x.device, needs_context=True)
         return self._scores(x, vps, context, text_mask, video_mask, 1., False)
 
 
@@ -499,19 +518,9 @@ class SelfCritic(PackedModule):
     def forward_with_cond_scale(self, *args, cond_scale=3, **kwargs):
         kwargs = dict(kwargs)
         x, vps = self.maskgit._prepare(args[0], kwargs.get('text_mask'), kwargs.pop('video_patch_shape', None))
-        b, n = x.shape
-        context, text_mask, video_mask = kwargs.get('context'), kwargs.get('text_mask'), kwargs.get('video_mask')
         with_null = cond_scale != 1
-        rep = lambda t: None if t is None else torch.cat((t, t), dim=0)
-        if with_null:
-            e = self.maskgit.embeds(x, replicas=2, video_patch_shape=vps, context=rep(context),
-                                    text_mask=rep(text_mask), video_mask=rep(video_mask), null_rows=b)
-        else:
-            e = self.maskgit.embeds(x, video_patch_shape=vps, context=context, text_mask=text_mask, video_mask=video_mask)
-        w, bias = self.head()
-        out = torch.empty((b, n), device=x.device, dtype=torch.float32)
-        L.critic_head(e, w, bias, e.shape[1], b, n, 0, with_null, float(cond_scale), None, 0., out)
-        return out
+        e = self.maskgit._cfg_embeds(x, vps, kwargs.get('context'), kwargs.get('text_mask'), kwargs.get('video_mask'), with_null)
+        return _critic_scores(self, e, *x.shape, with_null, cond_scale)
 
     def forward(self, x, *args, **kwargs):
         """phenaki_pytorch.py:334-336; under grad mode with trainable parameters: with an autograd graph (train.py)"""
@@ -528,10 +537,34 @@ class SelfCritic(PackedModule):
     def _forward_value(self, x, *args, **kwargs):
         embeds = self.maskgit(x, *args, return_embeds=True, **kwargs)
         b, n, d = embeds.shape
-        w, bias = self.head()
-        out = torch.empty((b, n), device=x.device, dtype=torch.float32)
-        L.critic_head(embeds.reshape(b * n, d), w, bias, d, b, n, 0, False, 1., None, 0., out)
-        return out
+        return _critic_scores(self, embeds.reshape(b * n, d), b, n)
+
+
+# what `Phenaki._masked_batch` / `Phenaki._sample_contexts` return; the fields are described there
+MaskedBatch = namedtuple('MaskedBatch', 'ids patch_shape text_embeds text_mask video_mask mask masked_ids rows')
+_SampleContexts = namedtuple('_SampleContexts', 'text_shape cond_scale with_null c_null ctx tm c_ctx c_tm P has_negative critic_guided')
+
+
+class _SampleState:
+    """everything `Phenaki._sample_loop` reads; a field that a call does not use is None.  The tensors are a captured graph's static inputs."""
+    __slots__ = (
+        'B', 'n', 'n_prime', 'patch_shape', 'prime_ids', 'prime_num_frames',        # n tokens to generate after n_prime prime tokens (B, n_prime)
+        'ks', 'compact', 'starting_temperature', 'critic_noise',                    # ks[s] tokens re-masked at step s; critic noise scale per step
+        'ids', 'mask', 'pred', 'scores', 'rows', 'partials', 'mixed',               # the loop's buffers (`Phenaki._sample_state`)
+        'contexts', 'table',                                                        # _SampleContexts; table path: (steps, P + 1, B) f32 on the device
+        'known', 'ks_dev', 'offs_dev', 'totals',                                    # infilling: known bytes (B, n) uint8, ks / offsets / row totals
+        'noise_fn', 'trace', 'force_fn',                                            # parity hooks (eager only)
+        'seed_base', 'seed_dev')                                                    # graph mode: the base seed lives in *seed_dev, else seed_dev is None
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields.pop(name, None))
+        assert not fields, f'unknown fields {sorted(fields)}'
+
+
+_M64 = 0xFFFFFFFFFFFFFFFF
+_head_seed = lambda seed_base, step: (seed_base + step * 0x9E3779B97F4A7C15) & _M64                 # pk_vocab_sample's stream at `step`
+_critic_seed = lambda seed_base, step: (seed_base + (2 * step + 1) * 0xD6E8FEB86659FD93) & _M64     # pk_critic_head's
 
 
 class Phenaki(PackedModule):
@@ -618,11 +651,16 @@ class Phenaki(PackedModule):
         critic_uses_text = need_critic and exists(critic) and (isinstance(critic, SelfCritic) or critic.has_cross_attn)
         return mg_mask, (dropped('critic_cond_keep') if critic_uses_text else text_mask)
 
-    def _masked_batch(self, videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws, mask_prob=None, generator=None):
-        """the inputs of the training call -> (ids (b, n) int64, patch shape, text_embeds, text_mask, video_mask, mask (b, n) bool, masked ids): the
-        tokenizer / text-encoder front end and the masking of phenaki_pytorch.py:580-628, shared by objective_value and evaluate.  The two draws
-        (schedule step, permutation noise) come from `draws` where it has them, else from `generator` (None: the device's default generator);
-        mask_prob replaces the cosine schedule by a fixed fraction."""
+    def _masked_batch(self, videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws, mask_prob=None, generator=None,
+                      host_counts=False):
+        """the inputs of the training call -> MaskedBatch(ids (b, n) int64, patch shape, text_embeds, text_mask, video_mask, mask (b, n) bool, masked
+        ids, rows): the tokenizer / text-encoder front end and the masking of phenaki_pytorch.py:580-628, shared by objective_value, evaluate
+        and the training step (train.py::phenaki_loss).  The two draws (schedule step, permutation noise) come from `draws` where it has
+        them, else from `generator` (None: the default generator); mask_prob replaces the cosine schedule by a fixed fraction.
+        host_counts=False: both draws on the ids' device, as the reference (:620); `rows` is None.
+        host_counts=True (the training step): the schedule step is drawn on the HOST, so the number of masked tokens per sample -- hence the
+        row count of the vocabulary head -- is known without reading anything back and the host can run a whole step ahead of the GPU; `rows`
+        (M,) int32 lists the masked positions (flat b * n + i, ascending).  Under a video mask the counts live on the device: one read-back."""
         assert exists(videos) ^ exists(video_codebook_ids), 'either raw video or video codebook ids must be given'
         assert not (exists(videos) and not exists(self.cvivit)), 'cvivit must be provided if one wants to encode the videos live during training'
         assert (exists(text_embeds) ^ exists(texts)) ^ self.unconditional, \
@@ -651,22 +689,34 @@ class Phenaki(PackedModule):
 
         ids = video_codebook_ids.reshape(video_codebook_ids.shape[0], -1).long().contiguous()
         b, n = ids.shape
+        step_device = 'cpu' if host_counts else device
         if exists(mask_prob):
-            mask_token_prob = torch.full((b,), float(mask_prob), device=device)
+            mask_token_prob = torch.full((b,), float(mask_prob), device=step_device)
         else:
-            rand_step = (draws['rand_step'].to(device) if 'rand_step' in draws
-                         else torch.randint(0, self.steps, (b,), device=device, generator=generator))
+            rand_step = (draws['rand_step'].to(step_device) if 'rand_step' in draws
+                         else torch.randint(0, self.steps, (b,), device=step_device, generator=generator))
             mask_token_prob = torch.cos(rand_step * math.pi * 0.5 / self.steps)
-        vm = video_mask if exists(video_mask) else torch.ones((b, n), device=device, dtype=torch.bool)
-        # get_mask_subset_with_prob (phenaki_pytorch.py:43-55)
-        num_tokens = vm.sum(dim=-1)
-        num_masked = (mask_token_prob * num_tokens).round().clamp(min=1)
         perm_noise = draws['perm_noise'].to(device) if 'perm_noise' in draws else torch.rand((b, n), device=device, generator=generator)
-        perm = perm_noise.argsort(dim=-1) - (n - num_tokens)[:, None]
-        perm = perm.masked_fill(perm < 0, n)
-        mask_token_mask = perm < num_masked[:, None]
+        # get_mask_subset_with_prob (phenaki_pytorch.py:43-55)
+        rows = None
+        if host_counts and not exists(video_mask):
+            num_masked = (mask_token_prob * n).round().clamp(min=1)
+            M = int(num_masked.sum())
+            # (pinned + non_blocking: a pageable host-to-device copy would wait for the stream, i.e. for the previous step)
+            mask_token_mask = perm_noise.argsort(dim=-1) < num_masked.pin_memory().to(device, non_blocking=True)[:, None]
+            # a stable sort lists the masked positions in ascending order, with a size the host already knows
+            rows = torch.argsort((~mask_token_mask).reshape(-1).to(torch.uint8), stable=True)[:M].int()
+        else:
+            vm = video_mask if exists(video_mask) else torch.ones((b, n), device=device, dtype=torch.bool)
+            num_tokens = vm.sum(dim=-1)
+            num_masked = (mask_token_prob.to(device) * num_tokens).round().clamp(min=1)
+            perm = perm_noise.argsort(dim=-1) - (n - num_tokens)[:, None]
+            perm = perm.masked_fill(perm < 0, n)
+            mask_token_mask = perm < num_masked[:, None]
+            if host_counts:
+                rows = mask_token_mask.reshape(-1).nonzero().reshape(-1).int()
         masked_input = torch.where(mask_token_mask, self.mask_id, ids)
-        return ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input
+        return MaskedBatch(ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input, rows)
 
     @torch.no_grad()
     def objective_value(self, videos=None, *, texts=None, video_codebook_ids=None, video_frame_mask=None, text_embeds=None,
@@ -683,16 +733,16 @@ class Phenaki(PackedModule):
         assert not (only_train_critic and not exists(self.critic)), 'only_train_critic needs a critic (Phenaki(critic=...) or self_token_critic=True)'
         mg, critic = self.maskgit, self.critic
         draws = _draws or {}
-        ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input = self._masked_batch(
-            videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws)
+        mb = self._masked_batch(videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws)
+        ids, mask_token_mask = mb.ids, mb.mask
         b, n = ids.shape
         device = ids.device
 
         dt = compute_dtype_of(mg)
         D, V = mg.dim, mg.to_logits.weight.shape[0]
         need_critic = exists(critic) and not only_train_generator
-        mg_text_mask, critic_text_mask = self._cond_drop_masks(text_mask, cond_drop_prob, draws, b, need_critic)
-        e = mg.embeds(masked_input, video_patch_shape=patch_shape, context=text_embeds, text_mask=mg_text_mask, video_mask=video_mask)
+        mg_text_mask, critic_text_mask = self._cond_drop_masks(mb.text_mask, cond_drop_prob, draws, b, need_critic)
+        e = mg.embeds(mb.masked_ids, video_patch_shape=mb.patch_shape, context=mb.text_embeds, text_mask=mg_text_mask, video_mask=mb.video_mask)
         # rows of the vocab head: the critic's labels compare the ids with the gumbel-sampled prediction at EVERY position
         # (phenaki_pytorch.py:653,671), so with a critic the head runs on all b*n rows; the generator-only objective needs
         # the masked rows only (>= 1 per sample, clamp(min=1) above)
@@ -721,8 +771,8 @@ class Phenaki(PackedModule):
         L.vocab_reduce(partials, M, V, None, None, None, pred, None, False)
         pred = pred.view(b, n)
         critic_input = torch.where(mask_token_mask, pred, ids)
-        crit = critic(critic_input.view(b, *patch_shape), video_mask=video_mask, cond_drop_prob=0., text_mask=critic_text_mask,
-                      context=text_embeds)
+        crit = critic(critic_input.view(b, *mb.patch_shape), video_mask=mb.video_mask, cond_drop_prob=0., text_mask=critic_text_mask,
+                      context=mb.text_embeds)
         labels = (ids != pred).float()
         critic_loss = torch.nn.functional.binary_cross_entropy_with_logits(crit.reshape(b, n), labels)
         if only_train_critic:
@@ -760,14 +810,14 @@ class Phenaki(PackedModule):
         if exists(mask_prob) and not 0. < float(mask_prob) <= 1.:
             raise ValueError(f'evaluate: mask_prob must be in (0, 1], got {mask_prob}')
         mg, critic = self.maskgit, self.critic
-        ids, patch_shape, text_embeds, text_mask, video_mask, mask_token_mask, masked_input = self._masked_batch(
-            videos, texts, video_codebook_ids, video_frame_mask, text_embeds, _draws or {}, mask_prob, generator)
+        mb = self._masked_batch(videos, texts, video_codebook_ids, video_frame_mask, text_embeds, _draws or {}, mask_prob, generator)
+        ids, mask_token_mask = mb.ids, mb.mask
         b, n = ids.shape
         device = ids.device
 
         dt = compute_dtype_of(mg)
         D, V = mg.dim, mg.to_logits.weight.shape[0]
-        e = mg.embeds(masked_input, video_patch_shape=patch_shape, context=text_embeds, text_mask=text_mask, video_mask=video_mask)
+        e = mg.embeds(mb.masked_ids, video_patch_shape=mb.patch_shape, context=mb.text_embeds, text_mask=mb.text_mask, video_mask=mb.video_mask)
         rows = mask_token_mask.reshape(-1).nonzero().reshape(-1).int()      # >= 1 per sample (clamp(min=1) above)
         M = rows.numel()
         mixed = torch.empty((M, D), device=device, dtype=L.tdtype(dt))
@@ -781,7 +831,7 @@ class Phenaki(PackedModule):
             filled = ids.reshape(-1).clone()
             filled[rows.long()] = out['pred']
             filled = filled.view(b, n)
-            crit = critic(filled.view(b, *patch_shape), video_mask=video_mask, cond_drop_prob=0., text_mask=text_mask, context=text_embeds)
+            crit = critic(filled.view(b, *mb.patch_shape), video_mask=mb.video_mask, cond_drop_prob=0., text_mask=mb.text_mask, context=mb.text_embeds)
             out['critic_logits'] = crit.reshape(b, n)
             out['critic_labels'] = ids != filled
         return out
@@ -802,66 +852,67 @@ class Phenaki(PackedModule):
         return self
 
     def _sample_loop(self, st):
-        """the mask-predict loop on prepared state `st` (device buffers + host scalars); kernels and allocations only, no host
+        """the mask-predict loop on prepared state `st` (_SampleState: device buffers + host scalars); kernels and allocations only, no host
         synchronisation and no torch elementwise ops: capturable as a hipGraph."""
         mg, critic = self.maskgit, self.critic
         dt = compute_dtype_of(mg)
-        B, n, n_tot, npr, V, D = st['B'], st['n'], st['n_tot'], st['n_prime'], st['V'], st['D']
-        ids, mask, pred, scores2 = st['ids'], st['mask'], st['pred'], st['scores']
-        rows_buf, partials, mixed = st['rows'], st['partials'], st['mixed']
-        ks, steps = st['ks'], self.steps
-        known = st.get('known')                                         # infilling (sample(known_ids=, known_mask=)): uint8 (B, n), else None
-        noise_fn, trace, seed_dev = st['noise_fn'], st['trace'], st['seed_dev']
-        seed_base = st['seed_base'] if seed_dev is None else 0          # graph mode: the base seed lives in *seed_dev
-        M64 = 0xFFFFFFFFFFFFFFFF
-        with_null, c_null = st['with_null'], st['c_null']
-        guided = st.get('guided')                                       # the table path (sample's guidance arguments): dict(P, J, critic_text), else None
-        c_guided = guided is not None and guided['critic_text']         # ... a critic that never sees the text keeps pk_critic_head
+        B, n, n_tot, npr, V, D = st.B, st.n, st.n + st.n_prime, st.n_prime, mg.to_logits.weight.shape[0], mg.dim
+        ids, mask, pred, mixed, partials = st.ids, st.mask, st.pred, st.mixed, st.partials
+        ks, steps, cx = st.ks, self.steps, st.contexts
+        noise_fn, seed_dev = st.noise_fn, st.seed_dev
+        seed_base = st.seed_base if seed_dev is None else 0             # graph mode: the base seed lives in *seed_dev
         need_lse = not exists(critic)
-        mg_cache, cr_cache = {}, {}
+        trunk_kw = dict(ids_prime=st.prime_ids, video_patch_shape=st.patch_shape)
+        mg_kw = dict(trunk_kw, context=cx.ctx, text_mask=cx.tm, kv_cache={})
+        cr_kw = dict(trunk_kw, context=cx.c_ctx, text_mask=cx.c_tm, kv_cache={})
+        # which mix and which critic head this run uses.  The table path: J = P + 1 branches [cond_0 | .. | cond_{P-1} | base] as one batch,
+        # mixed with the step's table row; the scalar path: [cond | null] (or cond alone) with the scale baked into the launch
+        if cx.P is not None:
+            mg_kw['replicas'] = cx.P + 1
+            mix = lambda e, rows, M, step: L.guidance_mix(e, B, n_tot, npr, rows, M, st.table[step], cx.P, True, mixed, D)
+        else:
+            mg_kw['replicas'] = 2 if cx.with_null else 1
+            mix = lambda e, rows, M, step: L.cfg_mix(e, B, n_tot, npr, rows, M, float(cx.cond_scale), cx.with_null, mixed, D)
+        if cx.critic_guided:
+            cr_kw['replicas'] = cx.P + 1
+            critic_head = lambda step, ce, w, bias, *tail, **seeds: L.critic_head_guided(
+                ce, w, bias, ce.shape[1], B, n_tot, npr, st.table[step], cx.P, True, *tail, **seeds)
+        else:
+            cr_kw['replicas'] = 2 if cx.c_null else 1
+            critic_head = lambda step, ce, w, bias, *tail, **seeds: L.critic_head(
+                ce, w, bias, ce.shape[1], B, n_tot, npr, cx.c_null, float(cx.cond_scale), *tail, **seeds)
         w_logits = linear_weight(mg.to_logits, dt)
-        have_scores = False
         for step in range(steps):
             is_last_step = step == (steps - 1)
-            steps_til_x0 = steps - (step + 1)
-            cur, nxt = scores2[step & 1], scores2[(step + 1) & 1]
+            cur, nxt = st.scores[step & 1], st.scores[(step + 1) & 1]
 
             rows, M = None, B * n
-            if known is not None:
+            if st.known is not None:
                 # infilling: re-mask among the FREE positions only, k_b(s) of them in sample b (known tokens are excluded by index, whatever
                 # their score); step 0 has no scores and k_b = F_b: it masks every free position and lists it, so the head never visits a
                 # known row.  The compact list is ragged: sample b's rows start at offs[s][b], M(s) = sum_b k_b(s) rows in all
-                if st['compact']:
-                    rows, M = rows_buf, st['totals'][step]
-                L.topk_mask_keep(cur if step > 0 else None, B, n, st['ks_dev'][step], st['offs_dev'][step], known, self.mask_id, mask, ids, rows,
+                if st.compact:
+                    rows, M = st.rows, st.totals[step]
+                L.topk_mask_keep(cur if step > 0 else None, B, n, st.ks_dev[step], st.offs_dev[step], st.known, self.mask_id, mask, ids, rows,
                                  scores_next=nxt if need_lse else None, k_host=ks[step], free_host=ks[0])
-            elif step > 0 and have_scores:
+            elif step > 0:
                 # mask + ids = where(mask, mask_id, ids); only the k_s re-masked positions need the vocab head this step
                 # (predictions elsewhere are discarded, phenaki_pytorch.py:509) -> compact row list for the head
-                if st['compact']:
-                    rows, M = rows_buf, B * ks[step]
+                if st.compact:
+                    rows, M = st.rows, B * ks[step]
                 L.topk_mask(cur, B, n, ks[step], self.mask_id, mask, ids, rows, scores_next=nxt if need_lse else None)
 
-            if st.get('force_fn') is not None:
+            if st.force_fn is not None:
                 # parity hook (eager only): the caller overwrites this step's masked ids / mask in place -- teacher forcing from a
                 # reference run's recorded inputs (tests: all 18 steps audited even after a near-tie changed a free-running input)
-                st['force_fn'](step, ids, mask)
+                st.force_fn(step, ids, mask)
 
             rec = None
-            if trace is not None:
-                rec = dict(step=step, masked_ids=ids.clone(), mask=mask.bool().clone(), prime_ids=st['prime_ids'])
+            if st.trace is not None:
+                rec = dict(step=step, masked_ids=ids.clone(), mask=mask.bool().clone(), prime_ids=st.prime_ids)
 
-            if guided is not None:
-                # the table path: J = P + 1 branches [cond_0 | .. | cond_{P-1} | base] as one batch, mixed with this step's table row
-                e = mg.embeds(ids, replicas=guided['J'], ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
-                              context=st['ctx_r'], text_mask=st['tm_r'], kv_cache=mg_cache)
-                L.guidance_mix(e, B, n_tot, npr, rows, M, st['table'][step], guided['P'], True, mixed, D)
-            else:
-                e = mg.embeds(ids, replicas=2 if with_null else 1, ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
-                              context=st['ctx_r'], text_mask=st['tm_r'], kv_cache=mg_cache)
-                L.cfg_mix(e, B, n_tot, npr, rows, M, float(st['cond_scale']), with_null, mixed, D)
-
-            temperature = st['starting_temperature'] * (steps_til_x0 / steps)
+            mix(mg.embeds(ids, **mg_kw), rows, M, step)
+            temperature = st.starting_temperature * ((steps - (step + 1)) / steps)
             U = noise_fn('gumbel', step, (B, n, V)) if noise_fn is not None else None
             if isinstance(U, L.TorchPhilox):
                 # torch's own RNG stream: the noise torch.zeros((B, n, V)).uniform_() would hold, generated in the epilogue; then the
@@ -870,65 +921,202 @@ class Phenaki(PackedModule):
                 U.advance()
             else:
                 L.vocab_sample(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, float(temperature), U, rows,
-                               (seed_base + step * 0x9E3779B97F4A7C15) & M64, need_lse, partials, seed_dev=seed_dev)
+                               _head_seed(seed_base, step), need_lse, partials, seed_dev=seed_dev)
             L.vocab_reduce(partials, M, V, rows, mask, ids, pred, nxt if need_lse else None, need_lse)
             if rec is not None:
                 rec.update(pred=pred.clone(), ids=ids.clone())
 
             if not is_last_step:
                 if exists(critic):
-                    ce = critic.embeds(ids, replicas=guided['J'] if c_guided else (2 if c_null else 1), ids_prime=st['prime_ids'], video_patch_shape=st['patch_shape'],
-                                       context=st['c_ctx_r'], text_mask=st['c_tm_r'], kv_cache=cr_cache)
-                    if self.critic_noise_anneal_schedule == 'fixed':
-                        noise_multiplier = 1.
-                    elif self.critic_noise_anneal_schedule == 'decay':
-                        noise_multiplier = steps_til_x0 / steps
-                    elif self.critic_noise_anneal_schedule == 'increase':
-                        noise_multiplier = (step + 1) / steps
-                    else:
-                        raise ValueError('invalid critic noise anneal schedule name')
+                    ce = critic.embeds(ids, **cr_kw)
                     u = noise_fn('critic', step, (B, n)).contiguous() if noise_fn is not None else None
-                    w, bias = critic.head()
-                    if c_guided:
-                        L.critic_head_guided(ce, w, bias, ce.shape[1], B, n_tot, npr, st['table'][step], guided['P'], True, u,
-                                             float(st['noise_K'] * noise_multiplier), nxt,
-                                             seed=(seed_base + (2 * step + 1) * 0xD6E8FEB86659FD93) & M64, seed_dev=seed_dev)
-                    else:
-                        L.critic_head(ce, w, bias, ce.shape[1], B, n_tot, npr, c_null, float(st['cond_scale']), u,
-                                      float(st['noise_K'] * noise_multiplier), nxt,
-                                      seed=(seed_base + (2 * step + 1) * 0xD6E8FEB86659FD93) & M64, seed_dev=seed_dev)
-                have_scores = True
+                    critic_head(step, ce, *critic.head(), u, st.critic_noise[step], nxt, seed=_critic_seed(seed_base, step), seed_dev=seed_dev)
                 if rec is not None:
                     rec['scores'] = nxt.clone()
             if rec is not None:
-                trace.append(rec)
+                st.trace.append(rec)
 
-        video = self.cvivit.decode_from_codebook_indices(ids, _prime_indices=st['prime_ids'])
-        if st['prime_ids'] is not None:
-            video = video[:, :, st['prime_num_frames']:]
+        video = self.cvivit.decode_from_codebook_indices(ids, _prime_indices=st.prime_ids)
+        if st.prime_ids is not None:
+            video = video[:, :, st.prime_num_frames:]
         return video
 
-    def _sample_state(self, B, n, n_prime, device, dt):
-        V = self.maskgit.to_logits.weight.shape[0]
-        D = self.maskgit.dim
-        return dict(B=B, n=n, n_prime=n_prime, n_tot=n + n_prime, V=V, D=D,
-                    ids=torch.empty((B, n), device=device, dtype=torch.int64),
-                    mask=torch.empty((B, n), device=device, dtype=torch.uint8),
-                    pred=torch.empty((B, n), device=device, dtype=torch.int64),
-                    scores=[torch.empty((B, n), device=device, dtype=torch.float32) for _ in range(2)],
-                    rows=torch.empty((B * n,), device=device, dtype=torch.int32),
-                    partials=torch.empty((5 * L.vocab_ntiles(V) * B * n,), device=device, dtype=torch.float32),
-                    mixed=torch.empty((B * n, D), device=device, dtype=L.tdtype(dt)))
+    def _sample_arguments(self, texts, B, num_frames, prime_frames, cond_scale, guidance_schedule, negative_texts, blend, known_ids, known_mask,
+                          noise_fn, noise_K, device):
+        """sample()'s arguments, checked on the host: every ValueError, before anything is tokenized, encoded or launched.  Returns
+        (plan: `_guidance_plan`; known: None or `_check_known`'s (ids, known bytes, free counts) -- the ONE host synchronisation of an infilling
+        call; noise_fn: the callable; critic_noise: the critic's noise scale per step, None without a critic)."""
+        plan = self._guidance_plan(texts, cond_scale, guidance_schedule, negative_texts, blend)
+        known = None
+        if exists(known_ids) or exists(known_mask):
+            if not (exists(known_ids) and exists(known_mask)):
+                raise ValueError('sample: give known_ids and known_mask together (or neither)')
+            if exists(prime_frames):
+                raise ValueError('sample: known_ids / known_mask cannot be combined with prime_frames')
+            known = _check_known(known_ids, known_mask, B, self.cvivit.get_video_patch_shape(num_frames),
+                                 self.maskgit.to_logits.weight.shape[0], device)
+        critic_noise = None
+        if exists(self.critic):
+            critic_noise = [float(noise_K * critic_noise_multiplier(self.critic_noise_anneal_schedule, s, self.steps)) for s in range(self.steps - 1)]
+        if isinstance(noise_fn, str):
+            # _noise_fn = 'torch': the reference's own noise -- torch's device generator, consumed in the reference's order (per step one
+            # uniform_ of (B, n, V) for gumbel_sample, phenaki_pytorch.py:88-93, then one of (B, n) for the critic scores, :69-70 / :541-543).
+            # The (B, n, V) fill is never materialised: the vocabulary head reproduces its elements from the Philox state (pk_vocab_sample_philox)
+            # and the generator is moved past it, so `torch.manual_seed(s); phenaki.sample(...)` draws what a reference run on this GPU draws.
+            assert noise_fn == 'torch', "_noise_fn: a callable or 'torch'"
 
-    def _sample_start(self, st, known_ids, known):
+            def noise_fn(kind, step, shape):
+                if kind == 'gumbel':
+                    return L.TorchPhilox(device, shape[0] * shape[1] * shape[2])
+                return torch.zeros(shape, device=device).float().uniform_(0, 1)
+        return plan, known, noise_fn, critic_noise
+
+    def _prime_tokens(self, prime_frames, prime_ids, device):
+        """(token ids (B, n_prime) of the prime frames, their frame count), (None, 0) without; `prime_ids` (tests) replaces the tokenizer's ids"""
+        if not exists(prime_frames):
+            return None, 0
+        ids = self.cvivit(prime_frames, return_only_codebook_ids=True)
+        ids = ids.reshape(ids.shape[0], -1).contiguous()
+        if prime_ids is not None:
+            assert tuple(prime_ids.shape) == tuple(ids.shape)
+            ids = prime_ids.to(device=device, dtype=ids.dtype).contiguous()
+        return ids, prime_frames.shape[2]
+
+    def _sample_contexts(self, texts, B, plan, cond_scale, device):
+        """encode the texts and lay out what MaskGit and the critic attend to, once per call: _SampleContexts(text_shape: the graph key's entry;
+        cond_scale; with_null / c_null: MaskGit / the critic runs [cond | null]; ctx (S, L, d) f32, tm (S, L) uint8: MaskGit's context and text
+        mask, c_ctx, c_tm: the critic's, None for a trunk that never sees a text; P, has_negative, critic_guided: the table path).
+        Scalar path (plan None, P None): classifier-free guidance runs the cond and null passes as ONE batch of 2B sequences, the null half
+        under an all-False text mask (phenaki_pytorch.py:188-190); cond_scale == 1 or no text leaves B sequences.
+        Table path: all J = P + 1 branches (the texts, the blend texts, then the base: the negative texts or the null branch) as one batch of
+        J B sequences on contexts zero-padded to the longest length, padded rows masked out (`guidance_contexts`); MaskGit and a critic that
+        sees the text (critic_guided; a text-blind one keeps pk_critic_head) share the one layout.  cond_scale is 1. and never read."""
+        mg, critic = self.maskgit, self.critic
+        text_embeds = text_mask = None
+        if exists(texts):
+            text_embeds = self.encode_texts(texts, output_device=device).to(device).float().contiguous()
+            text_mask = torch.any(text_embeds != 0, dim=-1)
+        if plan is not None:
+            conds = [(text_embeds, text_mask)] + [self._encode_branch(t, B, device) for t in plan['blend_texts']]
+            base = self._encode_branch(plan['negative_texts'], B, device) if plan['negative_texts'] is not None else None
+            ctx, tm = guidance_contexts(conds, base)
+            c_text = exists(critic) and (isinstance(critic, SelfCritic) or critic.has_cross_attn)
+            return _SampleContexts(tuple(ctx.shape), 1., False, False, ctx, tm, ctx if c_text else None, tm if c_text else None,
+                                   plan['P'], base is not None, c_text)
+        has_ctx = exists(text_embeds) and not mg.unconditional
+        with_null = has_ctx and cond_scale != 1
+        c_has_ctx = exists(critic) and exists(text_embeds) and critic.has_cross_attn
+        c_null = (c_has_ctx and cond_scale != 1) if not isinstance(critic, SelfCritic) else cond_scale != 1
+
+        def layout(sees_text, null):
+            if not sees_text:
+                return None, None
+            return (torch.cat((text_embeds, text_embeds), dim=0) if null else text_embeds).contiguous(), _cfg_masks(text_mask, B, null)
+
+        return _SampleContexts(None if text_embeds is None else tuple(text_embeds.shape), cond_scale, with_null, c_null,
+                               *layout(has_ctx, with_null), *layout(c_has_ctx, c_null), None, False, False)
+
+    def _sample_seed(self, noise_fn, seed):
+        """the 62-bit base seed of the in-kernel counter hash: drawn from torch's default (CPU) generator, offset per rank, or `seed` itself;
+        0 (and no draw) when the caller injects the noise.  Kept in `self._pk_last_seed`."""
+        seed_base = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise_fn is None else 0
+        if noise_fn is None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            # batch-sharded sampling: every rank draws from its own noise stream even under a common torch seed
+            seed_base = (seed_base + 0xD1B54A32D192ED03 * (torch.distributed.get_rank() + 1)) & 0x3FFFFFFFFFFFFFFF
+        if seed is not None:
+            seed_base = int(seed) & 0x3FFFFFFFFFFFFFFF
+        self.__dict__['_pk_last_seed'] = seed_base
+        return seed_base
+
+    def _sample_key(self, B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known):
+        """what a captured graph of the loop depends on (`_pk_sample_graphs`' key, kept in `_pk_last_sample_key`).  On the table path the
+        scales, schedule and weights live in the table, a static input refilled per call: the key names the launch structure only --
+        ('guided', P, has_negative, L) in place of the scale -- so calls that differ only in those replay one graph.  Infilling: the free
+        counts are part of the key; another mask with the same counts replays, other counts capture again."""
+        scale = float(cx.cond_scale) if cx.P is None else ('guided', cx.P, cx.has_negative, cx.text_shape[1])
+        key = (B, n, n_prime, prime_num_frames, tuple(patch_shape), cx.text_shape, scale, float(starting_temperature), float(noise_K), compact,
+               dt, str(device), self.steps, self.critic_noise_anneal_schedule, None if known is None else tuple(known[2]))
+        self.__dict__['_pk_last_sample_key'] = key
+        return key
+
+    def _sample_state(self, B, n, patch_shape, cx, plan, known, device, dt, static=False, **scalars):
+        """the loop's state with its buffers allocated.  static: the state of a captured graph -- it owns its contexts (their clones, refilled
+        per call by `_sample_graphed`; what was one tensor stays one) and keeps the base seed on the device."""
+        V, D = self.maskgit.to_logits.weight.shape[0], self.maskgit.dim
+        if static:
+            own = lambda t: None if t is None else t.clone()
+            ctx, tm = own(cx.ctx), own(cx.tm)
+            cx = cx._replace(ctx=ctx, tm=tm, c_ctx=ctx if cx.c_ctx is cx.ctx else own(cx.c_ctx), c_tm=tm if cx.c_tm is cx.tm else own(cx.c_tm))
+        st = _SampleState(B=B, n=n, patch_shape=patch_shape, ks=mask_schedule(n, self.steps), contexts=cx,
+                          ids=torch.empty((B, n), device=device, dtype=torch.int64),
+                          mask=torch.empty((B, n), device=device, dtype=torch.uint8),
+                          pred=torch.empty((B, n), device=device, dtype=torch.int64),
+                          scores=[torch.empty((B, n), device=device, dtype=torch.float32) for _ in range(2)],
+                          rows=torch.empty((B * n,), device=device, dtype=torch.int32),
+                          partials=torch.empty((5 * L.vocab_ntiles(V) * B * n,), device=device, dtype=torch.float32),
+                          mixed=torch.empty((B * n, D), device=device, dtype=L.tdtype(dt)), **scalars)
+        if plan is not None:
+            st.table = plan['table'].to(device)
+        if known is not None:
+            st.ks, offs, st.totals = infill_schedule(known[2], self.steps)
+            st.known = torch.empty_like(known[1])
+            st.ks_dev = torch.tensor(st.ks, dtype=torch.int32, device=device)
+            st.offs_dev = torch.tensor(offs, dtype=torch.int32, device=device)
+        if static:
+            st.seed_dev = torch.zeros((1,), device=device, dtype=torch.int64)
+        return st
+
+    def _sample_start(self, st, known):
         """the loop's starting state, in place (the buffers are a captured graph's static inputs): everything masked; or, when infilling,
         the caller's ids and known bytes -- step 0's pk_topk_mask_keep then lays the mask_id over the free positions"""
         if known is None:
-            st['ids'].fill_(self.mask_id)
-            st['mask'].fill_(1)
+            st.ids.fill_(self.mask_id)
+            st.mask.fill_(1)
         else:
-            st['ids'].copy_(known_ids)
-            st['known'].copy_(known)
+            st.ids.copy_(known[0])
+            st.known.copy_(known[1])
+
+    def _sample_graphed(self, key, make_state, cx, plan, prime_ids, known, seed_base, return_ids):
+        """run the loop through the graph cache `_pk_sample_graphs`: {key: dict(graph, st, video, fingerprint)}"""
+        device = next(self.parameters()).device
+        graphs = self.__dict__.setdefault('_pk_sample_graphs', {})
+        # a captured graph holds raw pointers to the live parameters AND to the packed copies derived from them: any change of a
+        # parameter (optimizer step, EMA update through the autograd-visible path, load_state_dict, .to()) re-captures
+        fp = param_fingerprint(self)
+        entry = graphs.get(key)
+        if entry is not None and entry['fingerprint'] != fp:
+            graphs.pop(key)
+            entry = None
+        if entry is not None:
+            # refill the graph's static inputs in place from this call's layout: contexts, table, prime ids
+            st = entry['st']
+            have = st.contexts
+            pairs = {id(d): (d, s) for d, s in ((have.ctx, cx.ctx), (have.tm, cx.tm), (have.c_ctx, cx.c_ctx), (have.c_tm, cx.c_tm)) if d is not None}
+            for dst, src in list(pairs.values()) + [(st.table, plan and plan['table']), (st.prime_ids, prime_ids)]:
+                if dst is not None:
+                    dst.copy_(src)
+            self._sample_start(st, known)
+            st.seed_dev.fill_(seed_base)
+        else:
+            # first call for this configuration: one eager pass (packs weights, fills the bias caches), then capture
+            st = make_state(static=True)
+            self._sample_start(st, known)
+            st.seed_dev.fill_(seed_base)
+            entry = dict(st=st, fingerprint=fp)
+            side = torch.cuda.Stream(device=device)
+            side.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.stream(side):
+                self._sample_loop(st)
+            torch.cuda.current_stream(device).wait_stream(side)
+            self._sample_start(st, known)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                entry['video'] = self._sample_loop(st)
+            entry['graph'] = graph
+            graphs[key] = entry
+        entry['graph'].replay()
+        video = entry['video'] if self.__dict__.get('_pk_sample_graph_static') else entry['video'].clone()
+        return (video, st.ids.clone()) if return_ids else video
 
     def _guidance_plan(self, texts, cond_scale, guidance_schedule, negative_texts, blend):
         """sample()'s guidance arguments, checked on the host (every ValueError of the table path, before anything is encoded or launched).
@@ -976,200 +1164,60 @@ class Phenaki(PackedModule):
     def sample(self, *, num_frames, texts=None, prime_frames=None, batch_size=1, cond_scale=3.,
                starting_temperature=0.9, noise_K=1., _noise_fn=None, _trace=None, _return_ids=False, _compact=None, _seed=None,
                _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None, guidance_schedule=None, negative_texts=None, blend=None):
-        """phenaki_pytorch.py:418-560.  `_noise_fn(kind, step, shape)` (tests) injects the U[0,1) draws of the
-        reference run ('gumbel' (B,n,V) and 'critic' (B,n), device f32 tensors); _noise_fn='torch': torch's device generator in the
-        reference's order (a seeded reference run on the same GPU draws the same noise); without it the noise comes from the
-        in-kernel counter hash seeded from torch's default (CPU) generator (`_seed`: the exact 64-bit stream seed instead;
-        the seed a call used is kept in `self._pk_last_seed`).  `_force_fn(step, ids, mask)` (tests) may overwrite a step's masked
-        input ids (B, n) int64 and mask (B, n) uint8 in place before the trunk runs (teacher forcing; eager, no row compaction);
-        `_prime_ids` (tests, with prime_frames given) replaces the token ids the tokenizer would produce for the prime frames.
+        """phenaki_pytorch.py:418-560: `num_frames` new frames for `texts` (a str or B strings; without texts `batch_size` samples), continuing
+        `prime_frames` if given.  Returns the video (B, C, num_frames, H, W).
+
+        Noise comes from an in-kernel counter hash seeded from torch's default (CPU) generator; the seed a call used is kept in
+        `self._pk_last_seed`.  With `enable_sample_graph` the whole call replays one captured graph per configuration.
 
         Infilling: `known_ids` (int64 token ids) and `known_mask` (bool, True = keep the token), both or neither, shaped (B, f, h, w) or
         (B, n) for (f, h, w) = get_video_patch_shape(num_frames); the mask may also be (f, h, w) or (n,), shared by the batch.  The known
-        tokens stay as given and are part of the decoded clip; only the free ones are sampled: the loop starts from
-        where(known, known_ids, mask_id), re-masks k_b(s) = mask_schedule(F_b, steps)[s] of sample b's F_b free tokens per step
-        (pk_topk_mask_keep: known positions are excluded by index, whatever the critic scores them) and the vocabulary head visits only
-        masked rows (sum_b F_b at step 0).  Not combined with prime_frames.  B is len(texts), or batch_size without texts.  Shape, dtype
-        and range errors (known ids outside [0, num_tokens), a sample with nothing to generate) are ValueErrors raised before anything
-        launches.  The free counts F_b are read from the device once per call: ONE host synchronisation that a plain call does not have.
-        With enable_sample_graph the counts are part of the configuration key: another mask with the same counts replays, other counts
-        capture again.
+        tokens stay as given and are part of the decoded clip; only the free ones are sampled, k_b(s) = mask_schedule(F_b, steps)[s] of sample
+        b's F_b free tokens re-masked per step.  Not combined with prime_frames.  The free counts F_b are read from the device once per call:
+        ONE host synchronisation that a plain call does not have.
 
-        Guidance.  `cond_scale`: a Python number (the scalar path: one scale for the batch and all steps, baked into pk_cfg_mix /
-        pk_critic_head), or a sequence / 1-D tensor of B finite floats, one per sample.  `guidance_schedule`: None, 'linear'
-        (m[s] = (s + 1) / steps) or `steps` finite floats m[s]; the scale of step s is 1 + (cond_scale[b] - 1) m[s].  `negative_texts`: a str
-        shared by the batch or B strings; the guidance then points away from that text's trunk output instead of the null branch's.
-        `blend`: up to two (texts_k, weight_k) pairs, texts_k a str (shared) or B strings, weight_k a float or B floats: the conditional
-        output becomes (1 - sum_k weight_k) e(texts) + sum_k weight_k e(texts_k).  Any of these, or a non-scalar cond_scale, selects the
-        table path: all J = P + 1 branches (P conditional, then the base) run as one batch of J B sequences on contexts zero-padded to the
-        longest length (padded rows masked out), and pk_guidance_mix / pk_critic_head_guided read the weights and scales from a
-        (steps, P + 1, B) f32 device table built on the host once per call; the base branch always runs.  Wrong lengths, non-finite values,
-        more than two blend entries, a guidance argument without texts or on an unconditional MaskGit are ValueErrors raised before
-        anything launches.  With enable_sample_graph the table and the padded contexts are static inputs refilled per call, and the key
-        carries ('guided', P, has_negative, L) in place of the scale: calls that differ only in scales, schedule or weights replay one graph."""
+        Guidance.  `cond_scale`: a Python number (the scalar path: one scale for the batch and all steps), or a sequence / 1-D tensor of B
+        finite floats, one per sample.  `guidance_schedule`: None, 'linear' (m[s] = (s + 1) / steps) or `steps` finite floats m[s]; the scale
+        of step s is 1 + (cond_scale[b] - 1) m[s].  `negative_texts`: a str shared by the batch or B strings; the guidance then points away
+        from that text's trunk output instead of the null branch's.  `blend`: up to two (texts_k, weight_k) pairs, texts_k a str (shared) or
+        B strings, weight_k a float or B floats: the conditional output becomes (1 - sum_k weight_k) e(texts) + sum_k weight_k e(texts_k).
+        Any of these, or a non-scalar cond_scale, selects the table path (`_sample_contexts`, `_sample_key`).
+
+        Shape, dtype, range and length errors (known ids outside [0, num_tokens), a sample with nothing to generate, non-finite values, more
+        than two blend entries, a guidance argument without texts or on an unconditional MaskGit, an unknown critic_noise_anneal_schedule)
+        are ValueErrors raised before anything launches (`_sample_arguments`).
+        Test hooks: `_noise_fn(kind, step, shape)` injects the U[0,1) draws of a reference run ('gumbel' (B,n,V) and 'critic' (B,n), device
+        f32 tensors); _noise_fn='torch': torch's device generator in the reference's order.  `_seed`: the exact 64-bit stream seed.
+        `_force_fn(step, ids, mask)` may overwrite a step's masked input ids (B, n) int64 and mask (B, n) uint8 in place before the trunk
+        runs (teacher forcing), `_trace` is a list that receives one record per step: both run eagerly without row compaction.  `_prime_ids`
+        replaces the token ids the tokenizer would produce for the prime frames; `_return_ids`: also return the sampled ids (B, n)."""
         device = next(self.parameters()).device
         L.require_device(next(self.parameters()), 'Phenaki parameters')
-        mg, critic = self.maskgit, self.critic
-        dt = compute_dtype_of(mg)
-        plan = self._guidance_plan(texts, cond_scale, guidance_schedule, negative_texts, blend)
-        known = free_counts = None
-        if exists(known_ids) or exists(known_mask):
-            if not (exists(known_ids) and exists(known_mask)):
-                raise ValueError('sample: give known_ids and known_mask together (or neither)')
-            if exists(prime_frames):
-                raise ValueError('sample: known_ids / known_mask cannot be combined with prime_frames')
-            nb = (1 if isinstance(texts, str) else len(texts)) if exists(texts) else batch_size
-            known_ids, known, free_counts = _check_known(known_ids, known_mask, nb, self.cvivit.get_video_patch_shape(num_frames),
-                                                         mg.to_logits.weight.shape[0], device)
-        if isinstance(_noise_fn, str):
-            # _noise_fn = 'torch': the reference's own noise -- torch's device generator, consumed in the reference's order (per step one
-            # uniform_ of (B, n, V) for gumbel_sample, phenaki_pytorch.py:88-93, then one of (B, n) for the critic scores, :69-70 / :541-543).
-            # The (B, n, V) fill is never materialised: the vocabulary head reproduces its elements from the Philox state (pk_vocab_sample_philox)
-            # and the generator is moved past it, so `torch.manual_seed(s); phenaki.sample(...)` draws what a reference run on this GPU draws.
-            assert _noise_fn == 'torch', "_noise_fn: a callable or 'torch'"
-
-            def _noise_fn(kind, step, shape):
-                if kind == 'gumbel':
-                    return L.TorchPhilox(device, shape[0] * shape[1] * shape[2])
-                return torch.zeros(shape, device=device).float().uniform_(0, 1)
-
-        has_prime = exists(prime_frames)
-        prime_token_ids = None
-        prime_token_length = 0
-        prime_num_frames = 0
-        if has_prime:
-            prime_token_ids = self.cvivit(prime_frames, return_only_codebook_ids=True)
-            prime_token_ids = prime_token_ids.reshape(prime_token_ids.shape[0], -1).contiguous()
-            if _prime_ids is not None:
-                assert tuple(_prime_ids.shape) == tuple(prime_token_ids.shape)
-                prime_token_ids = _prime_ids.to(device=device, dtype=prime_token_ids.dtype).contiguous()
-            prime_token_length = prime_token_ids.shape[-1]
-            prime_num_frames = prime_frames.shape[2]
-
-        num_tokens = self.cvivit.num_tokens_per_frames(num_frames, include_first_frame=not has_prime)
-
-        text_embeds = text_mask = None
-        if exists(texts):
-            if isinstance(texts, str):
-                texts = [texts]
-            text_embeds = self.encode_texts(texts, output_device=device)
-            text_embeds = text_embeds.to(device).float().contiguous()
-            text_mask = torch.any(text_embeds != 0, dim=-1)
-            batch_size = len(texts)
-
+        dt = compute_dtype_of(self.maskgit)
+        if isinstance(texts, str):
+            texts = [texts]
+        B = len(texts) if exists(texts) else batch_size
+        plan, known, noise_fn, critic_noise = self._sample_arguments(texts, B, num_frames, prime_frames, cond_scale, guidance_schedule,
+                                                                     negative_texts, blend, known_ids, known_mask, _noise_fn, noise_K, device)
+        prime_ids, prime_num_frames = self._prime_tokens(prime_frames, _prime_ids, device)
+        n_prime = 0 if prime_ids is None else prime_ids.shape[-1]
+        n = self.cvivit.num_tokens_per_frames(num_frames, include_first_frame=not exists(prime_frames))
         patch_shape = self.cvivit.get_video_patch_shape(num_frames + prime_num_frames, include_first_frame=True)
-        B, n = batch_size, num_tokens
-
-        # classifier-free guidance: the cond and null passes run as ONE batch of 2B sequences; context / masks of that batch
-        # are laid out once per call (the null half = an all-False text mask, phenaki_pytorch.py:188-190)
-        has_ctx = exists(text_embeds) and not mg.unconditional
-        guided = None
-        if plan is not None:
-            # the table path: every branch's context, zero-padded to the longest, laid out once per call as one (J B, L, d) batch
-            conds = [(text_embeds, text_mask)] + [self._encode_branch(t, B, device) for t in plan['blend_texts']]
-            base = self._encode_branch(plan['negative_texts'], B, device) if plan['negative_texts'] is not None else None
-            g_ctx, g_tm = guidance_contexts(conds, base)
-            guided = dict(P=plan['P'], J=plan['P'] + 1, has_negative=base is not None, L=g_ctx.shape[1],
-                          critic_text=exists(critic) and (isinstance(critic, SelfCritic) or critic.has_cross_attn))
-            cond_scale = 1.                                                    # not read on the table path (a text-blind critic: no mix)
-        with_null = has_ctx and cond_scale != 1
-        rep = lambda t: torch.cat((t, t), dim=0) if with_null else t
-        c_has_ctx = exists(critic) and exists(text_embeds) and critic.has_cross_attn
-        c_null = (c_has_ctx and cond_scale != 1) if not isinstance(critic, SelfCritic) else cond_scale != 1
-        crep = lambda t: torch.cat((t, t), dim=0) if c_null else t
-
-        seed_base = int(torch.randint(0, 2 ** 62, (1,)).item()) if _noise_fn is None else 0
-        if _noise_fn is None and torch.distributed.is_available() and torch.distributed.is_initialized():
-            # batch-sharded sampling: every rank draws from its own noise stream even under a common torch seed
-            seed_base = (seed_base + 0xD1B54A32D192ED03 * (torch.distributed.get_rank() + 1)) & 0x3FFFFFFFFFFFFFFF
-        if _seed is not None:
-            seed_base = int(_seed) & 0x3FFFFFFFFFFFFFFF
-        self.__dict__['_pk_last_seed'] = seed_base
+        cx = self._sample_contexts(texts, B, plan, cond_scale, device)
+        seed_base = self._sample_seed(noise_fn, _seed)
         compact = (_trace is None) if _compact is None else bool(_compact)    # traces record the prediction at EVERY position
         if _force_fn is not None:
             compact = False                                                    # the forced mask need not be the top-k one
-
-        use_graph = self.__dict__.get('_pk_sample_graph', False) and _noise_fn is None and _trace is None and _force_fn is None
-        key = (B, n, prime_token_length, prime_num_frames, tuple(patch_shape), None if text_embeds is None else tuple(text_embeds.shape),
-               float(cond_scale), float(starting_temperature), float(noise_K), compact, dt, str(device), self.steps,
-               self.critic_noise_anneal_schedule, None if known is None else tuple(free_counts))
-        if guided is not None:
-            # scales, schedule and weights live in the table (a static input): the key names the launch structure only
-            key = key[:5] + (tuple(g_ctx.shape), ('guided', guided['P'], guided['has_negative'], guided['L'])) + key[7:]
-        self.__dict__['_pk_last_sample_key'] = key
-        graphs = self.__dict__.setdefault('_pk_sample_graphs', {}) if use_graph else None
-        entry = graphs.get(key) if use_graph else None
-        # a captured graph holds raw pointers to the live parameters AND to the packed copies derived from them: any change of a
-        # parameter (optimizer step, EMA update through the autograd-visible path, load_state_dict, .to()) re-captures
-        fp = param_fingerprint(self) if use_graph else None
-        if entry is not None and entry['fingerprint'] != fp:
-            graphs.pop(key)
-            entry = None
-        if entry is not None:
-            st = entry['st']
-            if guided is not None:
-                st['ctx_r'].copy_(g_ctx)
-                st['tm_r'].copy_(g_tm)
-                st['table'].copy_(plan['table'])
-            elif has_ctx or c_has_ctx:
-                entry['text_embeds'].copy_(text_embeds)
-                entry['tm'].copy_(text_mask)
-                # the CFG layouts are views/derived copies of the static inputs: rebuild them in place
-                if st['ctx_r'] is not None:
-                    st['ctx_r'].copy_(rep(entry['text_embeds']))
-                    st['tm_r'].copy_(_cfg_masks(entry['tm'], B, with_null))
-                if st['c_ctx_r'] is not None:
-                    st['c_ctx_r'].copy_(crep(entry['text_embeds']))
-                    st['c_tm_r'].copy_(_cfg_masks(entry['tm'], B, c_null))
-            if has_prime:
-                st['prime_ids'].copy_(prime_token_ids)
-            self._sample_start(st, known_ids, known)
-            st['seed_dev'].fill_(seed_base)
-            entry['graph'].replay()
-            video = entry['video'] if self.__dict__.get('_pk_sample_graph_static') else entry['video'].clone()
-            return (video, st['ids'].clone()) if _return_ids else video
-
-        if use_graph and exists(text_embeds):
-            text_embeds, text_mask = text_embeds.clone(), text_mask.clone()        # they become the graph's static inputs
-        st = self._sample_state(B, n, prime_token_length, device, dt)
-        st.update(patch_shape=patch_shape, prime_ids=prime_token_ids, prime_num_frames=prime_num_frames, ks=mask_schedule(n, self.steps),
-                  cond_scale=cond_scale, starting_temperature=starting_temperature, noise_K=noise_K, compact=compact,
-                  noise_fn=_noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base, seed_dev=None, with_null=with_null, c_null=c_null,
-                  ctx_r=rep(text_embeds).contiguous() if has_ctx else None, tm_r=_cfg_masks(text_mask, B, with_null) if has_ctx else None,
-                  c_ctx_r=crep(text_embeds).contiguous() if c_has_ctx else None, c_tm_r=_cfg_masks(text_mask, B, c_null) if c_has_ctx else None)
-        if guided is not None:
-            # g_ctx / g_tm were built for this call (nobody else holds them): with a graph they and the table become its static inputs
-            c_text = guided['critic_text']
-            st.update(guided=guided, table=plan['table'].to(device), ctx_r=g_ctx, tm_r=g_tm, c_ctx_r=g_ctx if c_text else None,
-                      c_tm_r=g_tm if c_text else None)
-        if known is not None:
-            ks, offs, totals = infill_schedule(free_counts, self.steps)
-            st.update(ks=ks, totals=totals, known=torch.empty_like(known), ks_dev=torch.tensor(ks, dtype=torch.int32, device=device),
-                      offs_dev=torch.tensor(offs, dtype=torch.int32, device=device))
-        self._sample_start(st, known_ids, known)
-        if not use_graph:
-            video = self._sample_loop(st)
-            return (video, st['ids']) if _return_ids else video
-
-        # first call for this configuration: one eager pass (packs weights, fills the bias caches), then capture
-        st['seed_dev'] = torch.zeros((1,), device=device, dtype=torch.int64)
-        st['seed_dev'].fill_(seed_base)
-        entry = dict(st=st, text_embeds=text_embeds, tm=text_mask, fingerprint=fp)
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            self._sample_loop(st)
-        torch.cuda.current_stream(device).wait_stream(side)
-        self._sample_start(st, known_ids, known)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            entry['video'] = self._sample_loop(st)
-        entry['graph'] = graph
-        graphs[key] = entry
-        graph.replay()
-        video = entry['video'] if self.__dict__.get('_pk_sample_graph_static') else entry['video'].clone()
-        return (video, st['ids'].clone()) if _return_ids else video
-
+        key = self._sample_key(B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known)
+        make_state = partial(self._sample_state, B, n, patch_shape, cx, plan, known, device, dt, n_prime=n_prime, prime_ids=prime_ids,
+                             prime_num_frames=prime_num_frames, compact=compact, starting_temperature=starting_temperature,
+                             critic_noise=critic_noise, noise_fn=noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base)
+        if self.__dict__.get('_pk_sample_graph', False) and noise_fn is None and _trace is None and _force_fn is None:
+            return self._sample_graphed(key, make_state, cx, plan, prime_ids, known, seed_base, _return_ids)
+        st = make_state()
+        self._sample_start(st, known)
+        video = self._sample_loop(st)
+        return (video, st.ids) if _return_ids else video
 
     @eval_decorator
     @torch.no_grad()

@@ -31,7 +31,6 @@ from a (seed, offset) stream read off the device's default torch generator on th
 autograd ctx so that the backward kernels regenerate the mask (nothing is stored).  Inactive dropout passes no site: exactly the calls of a p = 0 module.
 The tokenizer's own reconstruction step is train_cvivit.py.
 """
-import math
 import os
 import weakref
 
@@ -898,18 +897,31 @@ def wants_grad(*modules):
     return torch.is_grad_enabled() and any(p.requires_grad for m in modules if m is not None for p in m.parameters())
 
 
+def maskgit_trunk_train(mg, ids2d, video_patch_shape, context, text_mask, video_mask):
+    """MaskGit's trunk with gradients: position bias, cross-attention unless unconditional, the gradient shrink on the embedding"""
+    return trunk_train(mg, ids2d, video_patch_shape, context=context, text_mask=text_mask, video_mask=video_mask, use_bias=True,
+                       use_cross=not mg.unconditional, alpha=mg.gradient_shrink_alpha)
+
+
+def critic_trunk_train(critic, ids2d, video_patch_shape, context, text_mask, video_mask):
+    """a critic's trunk with gradients -> ((b n, D) f32 rows of norm_out, the head's Linear): a SelfCritic runs MaskGit's trunk, a TokenCritic
+    its own, which sees the text only if it was built with cross-attention"""
+    from .phenaki import SelfCritic, TokenCritic
+    if isinstance(critic, SelfCritic):
+        return maskgit_trunk_train(critic.maskgit, ids2d, video_patch_shape, context, text_mask, video_mask), critic.to_pred[0]
+    assert isinstance(critic, TokenCritic)
+    e = trunk_train(critic, ids2d, video_patch_shape, context=context if critic.has_cross_attn else None, text_mask=text_mask,
+                    video_mask=video_mask, use_bias=False, use_cross=critic.has_cross_attn, alpha=1.0)
+    return e, critic.to_logits[0]
+
+
 def maskgit_forward_train(mg, x, *, cond_drop_prob=0., text_mask=None, video_mask=None, video_patch_shape=None, return_embeds=False, context=None):
     """MaskGit.forward (phenaki_pytorch.py:163-213) with an autograd graph: logits (b, n, num_tokens) or, return_embeds, the trunk output"""
-    from .phenaki import prob_mask_like
+    from .phenaki import cond_drop_text_mask
     x, vps = mg._prepare(x, text_mask, video_patch_shape)
     b, n = x.shape
-    if exists(context) and not exists(text_mask):
-        text_mask = torch.ones(context.shape[:2], device=x.device, dtype=torch.bool)
-    if cond_drop_prob > 0 and exists(text_mask):
-        keep_mask = prob_mask_like((b,), 1 - cond_drop_prob, device=x.device)
-        text_mask = keep_mask[:, None] & text_mask
-    e = trunk_train(mg, x, vps, context=context, text_mask=text_mask, video_mask=video_mask, use_bias=True, use_cross=not mg.unconditional,
-                    alpha=mg.gradient_shrink_alpha)
+    text_mask = cond_drop_text_mask(context, text_mask, cond_drop_prob, b, x.device, needs_context=False)
+    e = maskgit_trunk_train(mg, x, vps, context, text_mask, video_mask)
     if return_embeds:
         return e.view(b, n, mg.dim)
     logits = _Linear.apply(e, mg.to_logits.weight, mg.to_logits.bias, compute_dtype_of(mg))
@@ -918,23 +930,12 @@ def maskgit_forward_train(mg, x, *, cond_drop_prob=0., text_mask=None, video_mas
 
 def critic_forward_train(critic, x, *, text_mask=None, cond_drop_prob=None, context=None, video_mask=None, video_patch_shape=None):
     """TokenCritic.forward (phenaki_pytorch.py:265-302) / SelfCritic.forward (:334-336) with an autograd graph: scores (b, n)"""
-    from .phenaki import SelfCritic, prob_mask_like
-    if isinstance(critic, SelfCritic):
-        e = maskgit_forward_train(critic.maskgit, x, cond_drop_prob=cond_drop_prob or 0., text_mask=text_mask, video_mask=video_mask,
-                                  video_patch_shape=video_patch_shape, return_embeds=True, context=context)
-        b, n, D = e.shape
-        head = critic.to_pred[0]
-        return _RowDot.apply(e.reshape(b * n, D), head.weight, head.bias).view(b, n)
-    x, vps = critic._flatten(x, video_patch_shape)
+    from .phenaki import SelfCritic, cond_drop_text_mask
+    self_critic = isinstance(critic, SelfCritic)                       # it is MaskGit's forward, text-mask rule included, under another head
+    x, vps = critic.maskgit._prepare(x, text_mask, video_patch_shape) if self_critic else critic._flatten(x, video_patch_shape)
     b, n = x.shape
-    if exists(context) and not exists(text_mask):
-        text_mask = torch.ones(context.shape[:2], device=x.device, dtype=torch.bool)
-    if exists(context) and exists(cond_drop_prob) and cond_drop_prob > 0:
-        keep_mask = prob_mask_like((b,), 1 - cond_drop_prob, device=x.device)
-        text_mask = keep_mask[:, None] & text_mask
-    e = trunk_train(critic, x, vps, context=context if critic.has_cross_attn else None, text_mask=text_mask, video_mask=video_mask,
-                    use_bias=False, use_cross=critic.has_cross_attn, alpha=1.0)
-    head = critic.to_logits[0]
+    text_mask = cond_drop_text_mask(context, text_mask, cond_drop_prob, b, x.device, needs_context=not self_critic)
+    e, head = critic_trunk_train(critic, x, vps, context, text_mask, video_mask)
     return _RowDot.apply(e, head.weight, head.bias).view(b, n)
 
 
@@ -947,70 +948,25 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
     shadowing: cond_drop_prob = default(argument, ph.cond_drop_prob), and MaskGit and the critic EACH draw their own prob_mask_like((b,), 1 - p)
     (:188-189, :286-287) and AND it into the text mask (_draws: 'cond_keep' / 'critic_cond_keep', (b,) bool).  An unconditional model ignores the flag.
     ph.label_smoothing / ph.z_loss_weight regularise the masked-token cross entropy (`vocab_cross_entropy`); the critic's BCE is unchanged."""
-    from .phenaki import SelfCritic, TokenCritic
     require_train_dim_head(ph.maskgit, ph.critic)                       # before the tokenizer or anything else launches
     assert not (only_train_generator and only_train_critic)
     assert not (only_train_critic and not exists(ph.critic)), 'only_train_critic needs a critic (Phenaki(critic=...) or self_token_critic=True)'
-    assert exists(videos) ^ exists(video_codebook_ids), 'either raw video or video codebook ids must be given'
-    assert not (exists(videos) and not exists(ph.cvivit)), 'cvivit must be provided if one wants to encode the videos live during training'
-    assert (exists(text_embeds) ^ exists(texts)) ^ ph.unconditional, \
-        'either raw text of text embeds must be given, and if unconditional, none should be given'
-    assert not (exists(text_embeds) and text_embeds.shape[-1] != ph.text_embed_dim), 'text embedding dimension is not correct'
     mg, critic = ph.maskgit, ph.critic
+    need_critic = exists(critic) and not only_train_generator
+    draws = _draws or {}
     with torch.no_grad():
-        if not exists(video_codebook_ids):
-            assert videos.ndim in {4, 5}
-            if videos.ndim == 4:
-                videos = videos.unsqueeze(2)
-            video_codebook_ids = ph.cvivit(videos, return_only_codebook_ids=True)
-        L.require_device(video_codebook_ids, 'video_codebook_ids')
-        assert video_codebook_ids.ndim == 4, 'video codebook ids must be (batch, frames, height, width): MaskGit takes the patch shape from it'
-        device = video_codebook_ids.device
-        patch_shape = tuple(video_codebook_ids.shape[1:])
-        text_mask = None
-        if not ph.unconditional:
-            if not exists(text_embeds):
-                text_embeds = ph.encode_texts(texts, output_device=device)
-            text_embeds = text_embeds.to(device).float()
-            text_mask = torch.any(text_embeds != 0, dim=-1)
-        video_mask = None
-        if exists(video_frame_mask):
-            video_mask = ph.cvivit.calculate_video_token_mask(videos, video_frame_mask=video_frame_mask)
-        ids = video_codebook_ids.reshape(video_codebook_ids.shape[0], -1).long().contiguous()
+        mb = ph._masked_batch(videos, texts, video_codebook_ids, video_frame_mask, text_embeds, draws, host_counts=True)
+        ids, mask_token_mask, rows = mb.ids, mb.mask, mb.rows
         b, n = ids.shape
-        draws = _draws or {}
-        # the step index is drawn on the HOST (reference: on the device, :620): the number of masked tokens per sample -- hence the row
-        # count of the vocabulary head -- is then known without reading anything back, and the host can run a whole step ahead of the GPU
-        rand_step = draws['rand_step'].cpu() if 'rand_step' in draws else torch.randint(0, ph.steps, (b,))
-        mask_token_prob = torch.cos(rand_step * math.pi * 0.5 / ph.steps)
-        perm_noise = draws['perm_noise'].to(device) if 'perm_noise' in draws else torch.rand((b, n), device=device)
-        if exists(video_mask):                                                          # token counts live on the device: one read-back
-            vm = video_mask
-            num_tokens = vm.sum(dim=-1)                                                 # get_mask_subset_with_prob (phenaki_pytorch.py:43-55)
-            num_masked = (mask_token_prob.to(device) * num_tokens).round().clamp(min=1)
-            perm = perm_noise.argsort(dim=-1) - (n - num_tokens)[:, None]
-            perm = perm.masked_fill(perm < 0, n)
-            mask_token_mask = perm < num_masked[:, None]
-            rows = mask_token_mask.reshape(-1).nonzero().reshape(-1).int()
-        else:
-            num_masked_host = (mask_token_prob * n).round().clamp(min=1)
-            M_rows = int(num_masked_host.sum())
-            # (pinned + non_blocking: a pageable host-to-device copy would wait for the stream, i.e. for the previous step)
-            num_masked_dev = num_masked_host.pin_memory().to(device, non_blocking=True)
-            mask_token_mask = perm_noise.argsort(dim=-1) < num_masked_dev[:, None]
-            # the flat positions of the masked tokens in ascending order, with a size the host already knows (no nonzero() read-back)
-            rows = torch.argsort((~mask_token_mask).reshape(-1).to(torch.uint8), stable=True)[:M_rows].int()
-        masked_input = torch.where(mask_token_mask, ph.mask_id, ids)
-        mg_text_mask, critic_text_mask = ph._cond_drop_masks(text_mask, cond_drop_prob, draws, b, exists(critic) and not only_train_generator)
+        device = ids.device
+        mg_text_mask, critic_text_mask = ph._cond_drop_masks(mb.text_mask, cond_drop_prob, draws, b, need_critic)
 
     dt = compute_dtype_of(mg)
     D, V = mg.dim, mg.to_logits.weight.shape[0]
     ctx_mg = torch.no_grad() if only_train_critic else torch.enable_grad()
     with ctx_mg:
-        e = trunk_train(mg, masked_input, patch_shape, context=text_embeds, text_mask=mg_text_mask, video_mask=video_mask, use_bias=True,
-                        use_cross=not mg.unconditional, alpha=mg.gradient_shrink_alpha)
+        e = maskgit_trunk_train(mg, mb.masked_ids, mb.patch_shape, mb.text_embeds, mg_text_mask, mb.video_mask)
     loss = None
-    need_critic = exists(critic) and not only_train_generator
     head = None
     if mg.to_logits.weight.dtype == torch.float32 and mg.to_logits.weight.is_contiguous():
         head = linear_images(mg.to_logits, dt)                           # W and W^T images of the vocabulary head, one launch for both
@@ -1041,15 +997,7 @@ def phenaki_loss(ph, videos=None, *, texts=None, video_codebook_ids=None, video_
         pred = pred.view(b, n)
         critic_input = torch.where(mask_token_mask, pred, ids)
         labels = (ids != pred).float().reshape(-1).contiguous()
-    if isinstance(critic, SelfCritic):
-        ce = trunk_train(critic.maskgit, critic_input, patch_shape, context=text_embeds, text_mask=critic_text_mask, video_mask=video_mask, use_bias=True,
-                         use_cross=not critic.maskgit.unconditional, alpha=critic.maskgit.gradient_shrink_alpha)
-        head = critic.to_pred[0]
-    else:
-        assert isinstance(critic, TokenCritic)
-        ce = trunk_train(critic, critic_input, patch_shape, context=text_embeds if critic.has_cross_attn else None, text_mask=critic_text_mask,
-                         video_mask=video_mask, use_bias=False, use_cross=critic.has_cross_attn, alpha=1.0)
-        head = critic.to_logits[0]
+    ce, head = critic_trunk_train(critic, critic_input, mb.patch_shape, mb.text_embeds, critic_text_mask, mb.video_mask)
     critic_loss = _BCEHead.apply(ce, head.weight, head.bias, labels)
     if only_train_critic:
         return critic_loss

@@ -773,3 +773,37 @@ def test_gemm_splitk_matches_plain_product(dtype, tol):
             out = torch.empty((N, K), device='cuda')
             L.sum_batch(part, splits, out, N * K)
             close(out.cpu(), want + bias, tol, f'split-K x{splits}, 256-wide tiles + bias ({dtype}, rows {rows})')
+
+
+@pytest.mark.parametrize('frame_mask', [False, True])
+def test_masked_batch_host_counts_agrees_with_the_device_draw(frame_mask):
+    """Phenaki._masked_batch, the one front end of objective_value / evaluate (host_counts=False) and of the training step (host_counts=True:
+    the schedule step on the host, the masked rows listed without a read-back): on the same draws both modes mask the same tokens, the row list
+    is nonzero() of the mask in ascending order, and draws handed in consume nothing from the default generators.  Under a video frame mask
+    (the last token frame of sample 1 hidden) the host mode takes the device path."""
+    cv, mg, cr, ph = load_product('tiny', TINY)
+    H = TINY['cvivit']['image_size']
+    video = weights.synthetic_video(2, 5, H, H, seed=5).cuda()
+    fmask = torch.tensor([[True] * 5, [True] * 3 + [False] * 2]).cuda() if frame_mask else None
+    ctx = weights.synthetic_context(2, 6, TINY['maskgit']['dim_context'], seed=3).cuda()
+    draws = dict(rand_step=torch.tensor([1, 3]), perm_noise=weights.uniform_noise((2, 48), 710))
+    with torch.no_grad():
+        vids = cv(video, return_only_codebook_ids=True)
+        assert vids.shape == (2, 3, 4, 4)
+        src = dict(videos=video, video_codebook_ids=None) if frame_mask else dict(videos=None, video_codebook_ids=vids)
+        cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state()
+        dev = ph._masked_batch(texts=None, video_frame_mask=fmask, text_embeds=ctx, draws=draws, **src)
+        host = ph._masked_batch(texts=None, video_frame_mask=fmask, text_embeds=ctx, draws=draws, host_counts=True, **src)
+        assert torch.equal(torch.get_rng_state(), cpu_state) and torch.equal(torch.cuda.get_rng_state(), dev_state)
+    assert dev.rows is None and host.rows.dtype == torch.int32
+    assert torch.equal(dev.ids, vids.reshape(2, 48)) and torch.equal(host.ids, dev.ids)
+    assert torch.equal(host.mask, dev.mask) and torch.equal(host.masked_ids, dev.masked_ids)
+    assert torch.equal(dev.masked_ids, torch.where(dev.mask, ph.mask_id, dev.ids))
+    assert torch.equal(host.rows.long(), host.mask.reshape(-1).nonzero().reshape(-1))
+    assert dev.patch_shape == host.patch_shape == (3, 4, 4) and torch.equal(dev.text_mask, host.text_mask)
+    # get_mask_subset_with_prob: round(cos(pi/2 * step / steps) * tokens) of each sample's visible tokens, steps = 6
+    assert dev.mask.sum(dim=1).tolist() == ([46, 23] if frame_mask else [46, 34])
+    if frame_mask:
+        assert torch.equal(dev.video_mask, host.video_mask) and dev.video_mask.sum(dim=1).tolist() == [48, 32]
+    else:
+        assert dev.video_mask is None and host.video_mask is None
