@@ -319,6 +319,11 @@ __device__ __forceinline__ bool score(const AttnBwdArgs& p, int s, int h, int gi
     out = v;
     return true;
 }
+// A row whose keys are ALL masked (key mask and / or causal mask, no null keys): every admitted score is NEG_MAX, the softmax is uniform over the admitted
+// keys (attention.py:158-172) and lse = NEG_MAX + log(count) rounds back to NEG_MAX exactly, in the forward kernels and in kernel Q's own pass -- that is
+// how both kernels know the row.  __expf(sc - lse) would be 1 there, so P = 1 / count is written out, and dS = 0: masked_fill passes no gradient to a masked
+// score (on any other row a masked key has P = 0 and with it dS = 0 already).
+__device__ __forceinline__ float full_mask_p(const AttnBwdArgs& p) { return 1.0f / (float)(p.pack_n ? p.pack_n : p.nkt); }
 
 #define PK_ZERO4 {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}}
 #define PK_ZERO2 {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}}
@@ -464,7 +469,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     dp = drop_keep(dr, w, r & 3) ? dp * dr.scale : 0.f;
                 }
                 float sc, ds = 0.f;
-                if (score(p, s, h, gi, j, accS[nb][i], sc)) ds = __expf(sc - lse[i]) * (dp - Dl[i]);
+                if (score(p, s, h, gi, j, accS[nb][i], sc) && lse[i] != NEG_MAX) ds = __expf(sc - lse[i]) * (dp - Dl[i]);      // a fully masked row: dS = 0
                 Ps[(m0 + kq * 4 + i) * TLD + nb * 16 + r] = ds;
             }
         }
@@ -524,6 +529,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (int c = 0; c < 2; ++c) { to_operand(fkx[c], fk[c]); to_operand(fvx[c], fv[c]); }
     f32x4 accK[4] = PK_ZERO4;
     f32x4 accV[4] = PK_ZERO4;
+    const float p_full = full_mask_p(p);
     const int nqt_all = (p.n + QT - 1) / QT;
     const int qt0 = G > 1 ? gq * p.kv_chunk : 0;
     const int nqt = G > 1 ? (qt0 + p.kv_chunk < nqt_all ? qt0 + p.kv_chunk : nqt_all) : nqt_all;
@@ -555,19 +561,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int nb = 0; nb < 2; ++nb) {
             const int ci = nb * 16 + r, gi = i0 + ci;
             const float lse = lse_s[ci], Dr = D_s[ci];
+            const bool full = lse == NEG_MAX;                       // the whole row is masked: P = 1 / count, dS = 0
             uint32_t w = 0;
             if constexpr (DROP) w = drop_word(dr, drop_row(dr, (uint32_t)sh * (uint32_t)p.n + (uint32_t)gi), (uint32_t)(j0 + m0 + kq * 4) >> 2);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float sc;
                 pr[nb][i] = 0.f;
-                if (score(p, s, h, gi, j0 + m0 + kq * 4 + i, accS[nb][i], sc)) pr[nb][i] = __expf(sc - lse);
+                if (score(p, s, h, gi, j0 + m0 + kq * 4 + i, accS[nb][i], sc)) pr[nb][i] = full ? p_full : __expf(sc - lse);
                 if constexpr (DROP) {
                     const float ms = drop_keep(dr, w, i) ? dr.scale : 0.f;
-                    dsv[nb][i] = pr[nb][i] * (accP[nb][i] * ms - Dr);
+                    dsv[nb][i] = full ? 0.f : pr[nb][i] * (accP[nb][i] * ms - Dr);
                     PS[(m0 + kq * 4 + i) * TLQ + ci] = pr[nb][i] * ms;
                 } else {
-                    dsv[nb][i] = pr[nb][i] * (accP[nb][i] - Dr);
+                    dsv[nb][i] = full ? 0.f : pr[nb][i] * (accP[nb][i] - Dr);
                     PS[(m0 + kq * 4 + i) * TLQ + ci] = pr[nb][i];
                 }
             }

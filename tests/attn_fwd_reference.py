@@ -44,7 +44,8 @@ pk_attn_small runs every product in f32 VALU arithmetic: the same terms with p_r
 (SMALL_NORM_ULPS).
 
 Not covered: the forms reachable only through the tuning environment variables PK_ATTN_LDS_QF, PK_ATTN_PF and PK_ATTN_MAX_QF (read once per process), the
-dropout forward, the backward kernels, head widths 32 and 128 (tests/test_dim_head_gpu.py).  The fused projection kernels of qkv.hip / qkv_attn.hip are held
+dropout forward (tests/test_dropout_gpu.py), head widths 32 and 128 (tests/test_dim_head_gpu.py).  The backward kernels (csrc/attn_train.hip) are held the
+same way by tests/attn_bwd_reference.py, which builds on this module.  The fused projection kernels of qkv.hip / qkv_attn.hip are held
 the same way by tests/qkv_reference.py, which builds on this module."""
 import math
 import zlib

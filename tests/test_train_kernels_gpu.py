@@ -69,13 +69,13 @@ def _first_S(pred, what):
 ATTN_CASES = (['qf3_ragged', 'qf3_ragged_bias', 'qf3_even', 'qf2_wide', 'kv_split_uneven'] +
               [f'keys{n}_{v}' for n in (129, 191, 257) for v in ('plain', 'null2', 'null2_mask', 'causal')] +
               [f'packed{n}_{v}' for n in (1, 21, 31, 32) for v in ('plain', 'dS')] +
-              ['cross65_ctx64', 'cross65_ctx1'])
+              ['cross65_ctx64', 'cross65_ctx1', 'fullmask129'])
 
 
 def _attn_spec(case):
     """the shape of a case, with the dispatch condition it exists for asserted"""
     n_cu = _n_cu()
-    sp = dict(S=2, n=None, nnull=0, bias=False, mask=False, causal=False, n_ctx=None)
+    sp = dict(S=2, n=None, nnull=0, bias=False, mask=False, causal=False, n_ctx=None, full=False)
     if case.startswith('qf3'):
         n = 384 if case == 'qf3_even' else 320
         S = _first_S(lambda S: _train_fwd(S, HEADS, n)[1] > n_cu >= _train_fwd(S, HEADS, n)[2], 'the 48-row training forward')
@@ -104,6 +104,10 @@ def _attn_spec(case):
         assert (-(-n // 32)) % chunk != 0
         sp.update(S=S, n=n)
         sp['branch'] = dict(kv_split=G, chunk=chunk, nqt=-(-n // 32))
+    elif case == 'fullmask129':
+        sp.update(n=129, mask=True, full=True, bias=True)        # no null keys: every score row of the masked sequence is fully masked
+        assert sp['nnull'] == 0 and sp['S'] >= 2
+        sp['branch'] = dict(nk=129, fully_masked_sequences=1, rows=HEADS * 129)
     elif case.startswith('keys'):
         n, v = case[4:].split('_', 1)
         n = int(n)
@@ -156,6 +160,8 @@ def _inputs(sp, seed):
     elif sp['mask']:
         mask = torch.rand(S, n, generator=g) > 0.2
         mask[:, 0] = True
+        if sp.get('full'):
+            mask[-1] = False
     if sp['bias']:
         bias = torch.randn(HEADS, n, n, generator=g)
     return x, G, ctx, mask, bias
@@ -190,7 +196,8 @@ def test_attention_block_branches(case, dtype, tol):
     head reaches 32 rows past it -- the Q fragment rows are clamped there) with and without the bias matrix, and at n = 384 (nq_pad % 48 == 0);
     qf2_wide: 64 rows per wave above n_cu with the backward at kv_split = 1; kv_split_uneven: the backward's query tiles dealt to G workgroups
     with a short last chunk; keys*: ragged last key tiles with / without null keys, key mask, causal + ALiBi; packed*: pk_attn_bwd_ws's packed
-    (sequence, head) groups at 64 / n per tile and, with dS wanted (the bias gradient), the unpacked path; cross*: n != n_kv at a tile edge."""
+    (sequence, head) groups at 64 / n per tile and, with dS wanted (the bias gradient), the unpacked path; cross*: n != n_kv at a tile edge;
+    fullmask129: the last sequence's key mask is all False and there are no null keys -- uniform attention, no gradient to q, k or the bias from it."""
     from phenaki_pytorch_amd.attention import resolve_dtype
     from phenaki_pytorch_amd.train import attention_train
     sp = _attn_spec(case)
