@@ -388,6 +388,25 @@ int pk_vocab_sample_philox(int dtype, const void* A, int lda, const void* W, int
                            int need_lse, void* partials, void* stream);
 int pk_vocab_reduce(const void* partials, int M, int V, const int* rows, const unsigned char* mask, long long* ids,
                     long long* pred, float* scores, int need_lse, void* stream);
+/* Top-k filtered sampling on the f32 logits of a row slab (the reference's top_k helper, phenaki_pytorch.py:95-101, in front of
+ * gumbel_sample; Phenaki.sample(filter_thres=, top_k=)).  logits [M][ldl] f32 = pk_gemm of the head's operands.  Per row m:
+ *     cut  = the k-th largest of logits[m][0..V), counting multiplicity (k == V: -inf, no select);
+ *     kept = { v : logits[m][v] >= cut } as floats (-0.0 == +0.0); exact ties at the cut are ALL kept, so |kept| may exceed k
+ *            (torch.topk keeps an arbitrary k of them: the one difference);
+ *     pred = argmax over kept v of the noisy logit, pk_vocab_sample's expressions: U != NULL reads u from U[lrow][V] (PARITY), else the
+ *            counter hash at (seed (+ *seed_dev), lrow * V + v), the draws pk_vocab_sample makes for the same (seed, logical row, column);
+ *            T = max(temperature, 1e-10f); the first maximum wins.  lrow = rows ? rows[m] : row_base + m.
+ * need_lse is pk_vocab_sample's flag word: bit 0 = also max and sum exp over ALL V columns (the score stays the unfiltered distribution's
+ * 1 - softmax[pred]), bit 1 = no noise.  The write-out is pk_vocab_reduce's at r = lrow: pred[r], ids[r] = where(mask[r], pred, ids[r]),
+ * scores[r] = where(mask[r], 1 - p, -1e4) (bit 0 only).  cut_out [M] f32 / kept_out [M] int32 (or NULL): the row's cut and kept count.
+ * One workgroup of 1024 lanes holds a row in registers; exact MSB-first radix select; fixed-order reductions: two calls agree bit for bit.
+ * PK_EINVAL before any launch: k < 1 or k > V; V < 4, V > 65536 or V % 4; ldl < V or ldl % 4; M <= 0; logits or pred NULL; scores without
+ * bit 0; rows together with row_base != 0.  PK_EALIGN: logits or U off 16 bytes. */
+int pk_logits_topk_sample(const float* logits, long long ldl, int M, int V, int k, float temperature,
+                          const float* U, const int* rows, int row_base, unsigned long long seed,
+                          const unsigned long long* seed_dev, int need_lse /* bit 0 lse | bit 1 no noise */,
+                          const unsigned char* mask, long long* ids, long long* pred, float* scores,
+                          float* cut_out, int* kept_out, void* stream);
 
 /* The masked-token cross entropy of phenaki_pytorch.py:640-643 without the logits: after a pk_vocab_sample call with
  * need_lse bit 0 set, loss[m] = logsumexp_v(logits[m][:]) - logits[m][targets[r]] with r = rows ? rows[m] : m, where the

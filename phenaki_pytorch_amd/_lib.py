@@ -81,6 +81,7 @@ SIGNATURES = {
     'pk_vocab_sample_philox': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _ULL, _ULL, ctypes.c_uint, _I, _P, _P],
     'pk_vocab_sample': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _ULL, _P, _I, _P, _P],
     'pk_vocab_reduce': [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    'pk_logits_topk_sample': [_P, _LL, _I, _I, _I, _F, _P, _P, _I, _ULL, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     'pk_vocab_ce': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     'pk_vocab_ce_reg': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P],
     'pk_vocab_weight_mean_words': [_I, _I, _I],
@@ -852,6 +853,36 @@ def vocab_reduce(partials, M, V, rows, mask, ids, pred, scores, need_lse):
     rc = load().pk_vocab_reduce(ptr(partials), M, V, ptr(rows), ptr(mask), ptr(ids), ptr(pred), ptr(scores),
                                 1 if need_lse else 0, stream(partials))
     _check(rc, 'pk_vocab_reduce')
+
+
+def logits_topk_sample(logits, M, V, k, temperature, U, rows, row_base, seed, need_lse, mask, ids, pred, scores, *, no_noise=False, seed_dev=None,
+                       cut_out=None, kept_out=None):
+    """top-k filtered sampling on M rows of f32 logits (row stride logits.stride(-2)); see pk_logits_topk_sample in the header"""
+    rc = load().pk_logits_topk_sample(f32p(logits, 'logits', rows_ok=True), logits.stride(-2), M, V, int(k), temperature, ptr(U), ptr(rows), int(row_base),
+                                      seed & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), (1 if need_lse else 0) | (2 if no_noise else 0), ptr(mask), ptr(ids),
+                                      ptr(pred), ptr(scores), ptr(cut_out), ptr(kept_out), stream(logits))
+    _check(rc, 'pk_logits_topk_sample')
+
+
+FILTER_SLAB_MB = 256          # the fastest of 64 / 128 / 256 at 4608 and 9216 rows x 65 536 (profiles/filtered_sample_time.txt): 1024 rows per slab
+
+
+def filter_slab_rows(M, V):
+    """rows of the f32 logits slab of the filtered head: min(M, PK_FILTER_SLAB_MB * 2^20 // (4 V)), at least 1"""
+    mb = int(os.environ.get('PK_FILTER_SLAB_MB', FILTER_SLAB_MB))
+    return max(1, min(int(M), (mb << 20) // (4 * int(V))))
+
+
+def vocab_sample_filtered(dtype, A, W, bias, M, V, D, k, temperature, U, rows, seed, need_lse, mask, ids, pred, scores, slab, seed_dev=None):
+    """the vocabulary head with a top-k filter, slab by slab of R = slab.shape[0] rows: logits = A[m0:m0+Rc] @ W^T + bias into the (R, V) f32
+    slab (pk_gemm on the head's operand images), then logits_topk_sample on those rows under rows[m0:m0+Rc] (or row_base = m0).  Every size
+    is known on the host and nothing synchronises: capturable in a hipGraph."""
+    R = slab.shape[0]
+    for m0 in range(0, M, R):
+        Rc = min(R, M - m0)
+        gemm(dtype, A[m0:m0 + Rc], W, Rc, V, D, C=slab[:Rc], bias=bias)
+        logits_topk_sample(slab, Rc, V, k, temperature, U, rows[m0:m0 + Rc] if rows is not None else None, 0 if rows is not None else m0, seed,
+                           need_lse, mask, ids, pred, scores, seed_dev=seed_dev)
 
 
 def check_ce_regularisers(label_smoothing, z_loss_weight, who='vocab_cross_entropy'):

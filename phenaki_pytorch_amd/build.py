@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'csrc', '_obj')
 LIB = os.path.join(HERE, 'libphenaki_hip.so')
-SOURCES = ['gemm.hip', 'qkv.hip', 'qkv_attn.hip', 'norm.hip', 'patch.hip', 'patch_embed.hip', 'elementwise.hip', 'attn.hip', 'sampler.hip', 'train.hip',
+SOURCES = ['gemm.hip', 'qkv.hip', 'qkv_attn.hip', 'norm.hip', 'patch.hip', 'patch_embed.hip', 'elementwise.hip', 'attn.hip', 'sampler.hip', 'filter_sample.hip', 'train.hip',
            'attn_train.hip', 'conv.hip', 'lfq_aux.hip', 'vq_train.hip', 'step_tail.hip', 'vgg.hip', 'metrics.hip']
 HEADERS = ['common.hpp', 'gemm_core.hpp', 'gemm_dma.hpp', 'gemm_p8.hpp', 'gemm_resident.hpp']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC'] + os.environ.get('PK_EXTRA_HIPCC_FLAGS', '').split()

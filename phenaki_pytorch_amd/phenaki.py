@@ -554,6 +554,7 @@ class _SampleState:
         'contexts', 'table',                                                        # _SampleContexts; table path: (steps, P + 1, B) f32 on the device
         'known', 'ks_dev', 'offs_dev', 'totals',                                    # infilling: known bytes (B, n) uint8, ks / offsets / row totals
         'noise_fn', 'trace', 'force_fn',                                            # parity hooks (eager only)
+        'filter_k', 'slab',                                                         # top-k filter: k < V and the (R, V) f32 logits slab, else None
         'seed_base', 'seed_dev')                                                    # graph mode: the base seed lives in *seed_dev, else seed_dev is None
 
     def __init__(self, **fields):
@@ -914,7 +915,11 @@ class Phenaki(PackedModule):
             mix(mg.embeds(ids, **mg_kw), rows, M, step)
             temperature = st.starting_temperature * ((steps - (step + 1)) / steps)
             U = noise_fn('gumbel', step, (B, n, V)) if noise_fn is not None else None
-            if isinstance(U, L.TorchPhilox):
+            if st.filter_k is not None:
+                # top-k filter: the logits of a row slab exist, f32; the select, the draw and the reduce's write-out are one kernel
+                L.vocab_sample_filtered(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, st.filter_k, float(temperature), U, rows,
+                                        _head_seed(seed_base, step), need_lse, mask, ids, pred, nxt if need_lse else None, st.slab, seed_dev=seed_dev)
+            elif isinstance(U, L.TorchPhilox):
                 # torch's own RNG stream: the noise torch.zeros((B, n, V)).uniform_() would hold, generated in the epilogue; then the
                 # generator moves on as if that fill had happened (the reference's gumbel_noise, phenaki_pytorch.py:88-93)
                 L.vocab_sample_philox(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, float(temperature), rows, U, need_lse, partials)
@@ -922,7 +927,8 @@ class Phenaki(PackedModule):
             else:
                 L.vocab_sample(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, float(temperature), U, rows,
                                _head_seed(seed_base, step), need_lse, partials, seed_dev=seed_dev)
-            L.vocab_reduce(partials, M, V, rows, mask, ids, pred, nxt if need_lse else None, need_lse)
+            if st.filter_k is None:
+                L.vocab_reduce(partials, M, V, rows, mask, ids, pred, nxt if need_lse else None, need_lse)
             if rec is not None:
                 rec.update(pred=pred.clone(), ids=ids.clone())
 
@@ -942,10 +948,11 @@ class Phenaki(PackedModule):
         return video
 
     def _sample_arguments(self, texts, B, num_frames, prime_frames, cond_scale, guidance_schedule, negative_texts, blend, known_ids, known_mask,
-                          noise_fn, noise_K, device):
+                          noise_fn, noise_K, device, filter_thres=None, top_k=None):
         """sample()'s arguments, checked on the host: every ValueError, before anything is tokenized, encoded or launched.  Returns
         (plan: `_guidance_plan`; known: None or `_check_known`'s (ids, known bytes, free counts) -- the ONE host synchronisation of an infilling
-        call; noise_fn: the callable; critic_noise: the critic's noise scale per step, None without a critic)."""
+        call; noise_fn: the callable; critic_noise: the critic's noise scale per step, None without a critic; filter_k: `_filter_k`)."""
+        filter_k = self._filter_k(filter_thres, top_k, noise_fn)
         plan = self._guidance_plan(texts, cond_scale, guidance_schedule, negative_texts, blend)
         known = None
         if exists(known_ids) or exists(known_mask):
@@ -969,7 +976,27 @@ class Phenaki(PackedModule):
                 if kind == 'gumbel':
                     return L.TorchPhilox(device, shape[0] * shape[1] * shape[2])
                 return torch.zeros(shape, device=device).float().uniform_(0, 1)
-        return plan, known, noise_fn, critic_noise
+        return plan, known, noise_fn, critic_noise, filter_k
+
+    def _filter_k(self, filter_thres, top_k, noise_fn):
+        """the k of the top-k filter from sample()'s filter_thres / top_k: None for the plain path (no filter given, or one that keeps all V
+        columns).  filter_thres resolves as the reference's top_k helper writes it (phenaki_pytorch.py:97): k = max(int((1 - thres) * V), 1)."""
+        if filter_thres is None and top_k is None:
+            return None
+        V = self.maskgit.to_logits.weight.shape[0]
+        if filter_thres is not None and top_k is not None:
+            raise ValueError('sample: give filter_thres or top_k, not both')
+        if isinstance(noise_fn, str):
+            raise ValueError("sample: filter_thres / top_k cannot be combined with _noise_fn='torch' (the Philox stream has no filtered path)")
+        if top_k is not None:
+            if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= V:
+                raise ValueError(f'sample: top_k must be an int in [1, {V}], got {top_k!r}')
+            k = top_k
+        else:
+            if isinstance(filter_thres, bool) or not isinstance(filter_thres, (int, float)) or not (0. <= filter_thres < 1.):     # NaN fails the range
+                raise ValueError(f'sample: filter_thres must be a finite number in [0, 1), got {filter_thres!r}')
+            k = max(int((1 - filter_thres) * V), 1)
+        return None if k >= V else k
 
     def _prime_tokens(self, prime_frames, prime_ids, device):
         """(token ids (B, n_prime) of the prime frames, their frame count), (None, 0) without; `prime_ids` (tests) replaces the tokenizer's ids"""
@@ -1028,14 +1055,15 @@ class Phenaki(PackedModule):
         self.__dict__['_pk_last_seed'] = seed_base
         return seed_base
 
-    def _sample_key(self, B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known):
+    def _sample_key(self, B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known, filter_k=None):
         """what a captured graph of the loop depends on (`_pk_sample_graphs`' key, kept in `_pk_last_sample_key`).  On the table path the
         scales, schedule and weights live in the table, a static input refilled per call: the key names the launch structure only --
         ('guided', P, has_negative, L) in place of the scale -- so calls that differ only in those replay one graph.  Infilling: the free
-        counts are part of the key; another mask with the same counts replays, other counts capture again."""
+        counts are part of the key; another mask with the same counts replays, other counts capture again.  The resolved k of a top-k filter
+        (None on the plain path) is the last entry: another k is another kernel argument and captures another graph."""
         scale = float(cx.cond_scale) if cx.P is None else ('guided', cx.P, cx.has_negative, cx.text_shape[1])
         key = (B, n, n_prime, prime_num_frames, tuple(patch_shape), cx.text_shape, scale, float(starting_temperature), float(noise_K), compact,
-               dt, str(device), self.steps, self.critic_noise_anneal_schedule, None if known is None else tuple(known[2]))
+               dt, str(device), self.steps, self.critic_noise_anneal_schedule, None if known is None else tuple(known[2]), filter_k)
         self.__dict__['_pk_last_sample_key'] = key
         return key
 
@@ -1053,8 +1081,11 @@ class Phenaki(PackedModule):
                           pred=torch.empty((B, n), device=device, dtype=torch.int64),
                           scores=[torch.empty((B, n), device=device, dtype=torch.float32) for _ in range(2)],
                           rows=torch.empty((B * n,), device=device, dtype=torch.int32),
-                          partials=torch.empty((5 * L.vocab_ntiles(V) * B * n,), device=device, dtype=torch.float32),
+                          partials=(torch.empty((5 * L.vocab_ntiles(V) * B * n,), device=device, dtype=torch.float32)
+                                    if scalars.get('filter_k') is None else None),            # the filtered head has the slab instead
                           mixed=torch.empty((B * n, D), device=device, dtype=L.tdtype(dt)), **scalars)
+        if st.filter_k is not None:
+            st.slab = torch.empty((L.filter_slab_rows(B * n, V), V), device=device, dtype=torch.float32)
         if plan is not None:
             st.table = plan['table'].to(device)
         if known is not None:
@@ -1163,7 +1194,8 @@ class Phenaki(PackedModule):
     @torch.no_grad()
     def sample(self, *, num_frames, texts=None, prime_frames=None, batch_size=1, cond_scale=3.,
                starting_temperature=0.9, noise_K=1., _noise_fn=None, _trace=None, _return_ids=False, _compact=None, _seed=None,
-               _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None, guidance_schedule=None, negative_texts=None, blend=None):
+               _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None, guidance_schedule=None, negative_texts=None, blend=None,
+               filter_thres=None, top_k=None):
         """phenaki_pytorch.py:418-560: `num_frames` new frames for `texts` (a str or B strings; without texts `batch_size` samples), continuing
         `prime_frames` if given.  Returns the video (B, C, num_frames, H, W).
 
@@ -1183,6 +1215,12 @@ class Phenaki(PackedModule):
         B strings, weight_k a float or B floats: the conditional output becomes (1 - sum_k weight_k) e(texts) + sum_k weight_k e(texts_k).
         Any of these, or a non-scalar cond_scale, selects the table path (`_sample_contexts`, `_sample_key`).
 
+        Top-k filtering.  `filter_thres` (a finite number in [0, 1); k = max(int((1 - filter_thres) * V), 1), the reference's top_k helper,
+        phenaki_pytorch.py:95-101) or `top_k` (an int in [1, V]), not both: every draw of the vocabulary head is taken from the columns whose
+        logit is >= the row's k-th largest (exact ties at the cut are all kept; torch.topk keeps an arbitrary k of them).  The confidence score
+        of a critic-less run stays 1 - p under the unfiltered softmax.  k = V, or neither argument, is the plain path: the logits are never
+        formed.  With a filter they are, one (R, V) f32 slab at a time (`_lib.vocab_sample_filtered`).  Not combined with _noise_fn='torch'.
+
         Shape, dtype, range and length errors (known ids outside [0, num_tokens), a sample with nothing to generate, non-finite values, more
         than two blend entries, a guidance argument without texts or on an unconditional MaskGit, an unknown critic_noise_anneal_schedule)
         are ValueErrors raised before anything launches (`_sample_arguments`).
@@ -1197,8 +1235,9 @@ class Phenaki(PackedModule):
         if isinstance(texts, str):
             texts = [texts]
         B = len(texts) if exists(texts) else batch_size
-        plan, known, noise_fn, critic_noise = self._sample_arguments(texts, B, num_frames, prime_frames, cond_scale, guidance_schedule,
-                                                                     negative_texts, blend, known_ids, known_mask, _noise_fn, noise_K, device)
+        plan, known, noise_fn, critic_noise, filter_k = self._sample_arguments(texts, B, num_frames, prime_frames, cond_scale, guidance_schedule,
+                                                                               negative_texts, blend, known_ids, known_mask, _noise_fn, noise_K,
+                                                                               device, filter_thres, top_k)
         prime_ids, prime_num_frames = self._prime_tokens(prime_frames, _prime_ids, device)
         n_prime = 0 if prime_ids is None else prime_ids.shape[-1]
         n = self.cvivit.num_tokens_per_frames(num_frames, include_first_frame=not exists(prime_frames))
@@ -1208,10 +1247,10 @@ class Phenaki(PackedModule):
         compact = (_trace is None) if _compact is None else bool(_compact)    # traces record the prediction at EVERY position
         if _force_fn is not None:
             compact = False                                                    # the forced mask need not be the top-k one
-        key = self._sample_key(B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known)
+        key = self._sample_key(B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known, filter_k)
         make_state = partial(self._sample_state, B, n, patch_shape, cx, plan, known, device, dt, n_prime=n_prime, prime_ids=prime_ids,
                              prime_num_frames=prime_num_frames, compact=compact, starting_temperature=starting_temperature,
-                             critic_noise=critic_noise, noise_fn=noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base)
+                             critic_noise=critic_noise, noise_fn=noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base, filter_k=filter_k)
         if self.__dict__.get('_pk_sample_graph', False) and noise_fn is None and _trace is None and _force_fn is None:
             return self._sample_graphed(key, make_state, cx, plan, prime_ids, known, seed_base, _return_ids)
         st = make_state()
