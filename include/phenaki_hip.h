@@ -407,6 +407,33 @@ int pk_logits_topk_sample(const float* logits, long long ldl, int M, int V, int 
                           const unsigned long long* seed_dev, int need_lse /* bit 0 lse | bit 1 no noise */,
                           const unsigned char* mask, long long* ids, long long* pred, float* scores,
                           float* cut_out, int* kept_out, void* stream);
+/* Nucleus (top-p) and min-p filtered sampling on the same logits (Phenaki.sample(top_p=, min_p=)); the reference has neither.  Everything
+ * pk_logits_topk_sample says about logits, U, rows, row_base, seed, seed_dev, need_lse, mask, ids, pred, scores and the write-out holds.
+ * Per row, l[v] the f32 logit, T = max(temperature, 1e-10f), inv_t = 1.0f / T, lmax the row maximum:
+ *     arg[v] = (l[v] - lmax) * inv_t in f32;  w[v] = __expf(arg[v]);  q[v] = (unsigned long long)(w[v] * 2^40), the fixed-point mass
+ *              (at most 2^40 per column, at most 2^56 over V <= 65 536 columns).
+ * The filters apply in the order temperature, top-k, top-p, min-p and the result is their intersection:
+ *     1. top-k: cut_k = the k-th largest logit counting multiplicity, S = { v : l[v] >= cut_k };  k == V: no top-k.
+ *     2. top-p: Z_S = sum_{v in S} q[v];  cut_p = the largest row value c such that sum_{v in S, l[v] >= c} q[v] >= top_p * Z_S: the smallest
+ *        descending prefix of S that reaches the share top_p of S's own mass.  Exact ties at the cut are all kept.  The product and the
+ *        comparison are done in double.  top_p == 1: no nucleus.  The maximum has q = 2^40 > 0: at least one column is kept.
+ *     3. min-p: v passes iff arg[v] >= (float)log((double)min_p) (taken on the host side of this entry point): the f32 arg is compared,
+ *        not w; arg is non-decreasing in l, so what passes is upward-closed.  min_p == 0: none.
+ *     4. kept = S & { l >= cut_p } & { min-p passes } = { v : l[v] >= cut }, cut the smallest kept logit: cut_out[m] (-inf when no filter
+ *        is active), kept_out[m] the count.
+ *     5. the draw and the score are pk_logits_topk_sample's: pred = argmax over kept v of the noisy logit, first maximum; the score stays
+ *        1 - softmax[pred] over ALL V columns at temperature 1.
+ * The nucleus is that of softmax(l / T) at the step's annealed temperature, the distribution the gumbel arg-max samples from; at
+ * temperature 0 (the clamp) it is the row maximum and its exact ties.
+ * The mass is accumulated as 64-bit integers (integer LDS atomics, four 8-bit MSB-first passes over the keys >= cut_k): no float atomics,
+ * every reduction in a fixed order, two calls agree bit for bit.  top_p == 1 && min_p == 0 gives pk_logits_topk_sample's bits for the same k.
+ * PK_EINVAL before any launch: top_p not in (0, 1] or NaN; min_p not in [0, 1) or NaN; whatever pk_logits_topk_sample refuses.  PK_EALIGN
+ * as there.  Finite logits only. */
+int pk_logits_nucleus_sample(const float* logits, long long ldl, int M, int V, int k, float top_p, float min_p, float temperature,
+                             const float* U, const int* rows, int row_base, unsigned long long seed,
+                             const unsigned long long* seed_dev, int need_lse /* bit 0 lse | bit 1 no noise */,
+                             const unsigned char* mask, long long* ids, long long* pred, float* scores,
+                             float* cut_out, int* kept_out, void* stream);
 
 /* The masked-token cross entropy of phenaki_pytorch.py:640-643 without the logits: after a pk_vocab_sample call with
  * need_lse bit 0 set, loss[m] = logsumexp_v(logits[m][:]) - logits[m][targets[r]] with r = rows ? rows[m] : m, where the

@@ -82,6 +82,7 @@ SIGNATURES = {
     'pk_vocab_sample': [_I, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _ULL, _P, _I, _P, _P],
     'pk_vocab_reduce': [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     'pk_logits_topk_sample': [_P, _LL, _I, _I, _I, _F, _P, _P, _I, _ULL, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    'pk_logits_nucleus_sample': [_P, _LL, _I, _I, _I, _F, _F, _F, _P, _P, _I, _ULL, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     'pk_vocab_ce': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     'pk_vocab_ce_reg': [_I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P],
     'pk_vocab_weight_mean_words': [_I, _I, _I],
@@ -883,6 +884,27 @@ def vocab_sample_filtered(dtype, A, W, bias, M, V, D, k, temperature, U, rows, s
         gemm(dtype, A[m0:m0 + Rc], W, Rc, V, D, C=slab[:Rc], bias=bias)
         logits_topk_sample(slab, Rc, V, k, temperature, U, rows[m0:m0 + Rc] if rows is not None else None, 0 if rows is not None else m0, seed,
                            need_lse, mask, ids, pred, scores, seed_dev=seed_dev)
+
+
+def logits_nucleus_sample(logits, M, V, k, top_p, min_p, temperature, U, rows, row_base, seed, need_lse, mask, ids, pred, scores, *, no_noise=False,
+                          seed_dev=None, cut_out=None, kept_out=None):
+    """top-k / nucleus / min-p filtered sampling on M rows of f32 logits (row stride logits.stride(-2)); see pk_logits_nucleus_sample in the header"""
+    rc = load().pk_logits_nucleus_sample(f32p(logits, 'logits', rows_ok=True), logits.stride(-2), M, V, int(k), float(top_p), float(min_p), temperature,
+                                         ptr(U), ptr(rows), int(row_base), seed & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev),
+                                         (1 if need_lse else 0) | (2 if no_noise else 0), ptr(mask), ptr(ids), ptr(pred), ptr(scores), ptr(cut_out),
+                                         ptr(kept_out), stream(logits))
+    _check(rc, 'pk_logits_nucleus_sample')
+
+
+def vocab_sample_nucleus(dtype, A, W, bias, M, V, D, k, top_p, min_p, temperature, U, rows, seed, need_lse, mask, ids, pred, scores, slab, seed_dev=None):
+    """vocab_sample_filtered with the adaptive filters: the same slab walk, logits_nucleus_sample on each slab's rows (k = V: no top-k, top_p = 1:
+    no nucleus, min_p = 0: no min-p).  Nothing synchronises: capturable in a hipGraph."""
+    R = slab.shape[0]
+    for m0 in range(0, M, R):
+        Rc = min(R, M - m0)
+        gemm(dtype, A[m0:m0 + Rc], W, Rc, V, D, C=slab[:Rc], bias=bias)
+        logits_nucleus_sample(slab, Rc, V, k, top_p, min_p, temperature, U, rows[m0:m0 + Rc] if rows is not None else None,
+                              0 if rows is not None else m0, seed, need_lse, mask, ids, pred, scores, seed_dev=seed_dev)
 
 
 def check_ce_regularisers(label_smoothing, z_loss_weight, who='vocab_cross_entropy'):

@@ -555,6 +555,7 @@ class _SampleState:
         'known', 'ks_dev', 'offs_dev', 'totals',                                    # infilling: known bytes (B, n) uint8, ks / offsets / row totals
         'noise_fn', 'trace', 'force_fn',                                            # parity hooks (eager only)
         'filter_k', 'slab',                                                         # top-k filter: k < V and the (R, V) f32 logits slab, else None
+        'nucleus',                                                                  # an active nucleus filter: (top_p, min_p) floats, else None
         'seed_base', 'seed_dev')                                                    # graph mode: the base seed lives in *seed_dev, else seed_dev is None
 
     def __init__(self, **fields):
@@ -915,7 +916,12 @@ class Phenaki(PackedModule):
             mix(mg.embeds(ids, **mg_kw), rows, M, step)
             temperature = st.starting_temperature * ((steps - (step + 1)) / steps)
             U = noise_fn('gumbel', step, (B, n, V)) if noise_fn is not None else None
-            if st.filter_k is not None:
+            if st.nucleus is not None:
+                # top-p / min-p (and a top-k, k = V without): the filtered head with the mass select in front of the draw
+                L.vocab_sample_nucleus(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, V if st.filter_k is None else st.filter_k, st.nucleus[0],
+                                       st.nucleus[1], float(temperature), U, rows, _head_seed(seed_base, step), need_lse, mask, ids, pred,
+                                       nxt if need_lse else None, st.slab, seed_dev=seed_dev)
+            elif st.filter_k is not None:
                 # top-k filter: the logits of a row slab exist, f32; the select, the draw and the reduce's write-out are one kernel
                 L.vocab_sample_filtered(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, st.filter_k, float(temperature), U, rows,
                                         _head_seed(seed_base, step), need_lse, mask, ids, pred, nxt if need_lse else None, st.slab, seed_dev=seed_dev)
@@ -927,7 +933,7 @@ class Phenaki(PackedModule):
             else:
                 L.vocab_sample(dt, mixed, w_logits, mg.to_logits.bias, M, V, D, float(temperature), U, rows,
                                _head_seed(seed_base, step), need_lse, partials, seed_dev=seed_dev)
-            if st.filter_k is None:
+            if st.filter_k is None and st.nucleus is None:
                 L.vocab_reduce(partials, M, V, rows, mask, ids, pred, nxt if need_lse else None, need_lse)
             if rec is not None:
                 rec.update(pred=pred.clone(), ids=ids.clone())
@@ -948,11 +954,13 @@ class Phenaki(PackedModule):
         return video
 
     def _sample_arguments(self, texts, B, num_frames, prime_frames, cond_scale, guidance_schedule, negative_texts, blend, known_ids, known_mask,
-                          noise_fn, noise_K, device, filter_thres=None, top_k=None):
+                          noise_fn, noise_K, device, filter_thres=None, top_k=None, top_p=None, min_p=None):
         """sample()'s arguments, checked on the host: every ValueError, before anything is tokenized, encoded or launched.  Returns
         (plan: `_guidance_plan`; known: None or `_check_known`'s (ids, known bytes, free counts) -- the ONE host synchronisation of an infilling
-        call; noise_fn: the callable; critic_noise: the critic's noise scale per step, None without a critic; filter_k: `_filter_k`)."""
+        call; noise_fn: the callable; critic_noise: the critic's noise scale per step, None without a critic; filter_k: `_filter_k`; nucleus:
+        `_filter_nucleus`)."""
         filter_k = self._filter_k(filter_thres, top_k, noise_fn)
+        nucleus = self._filter_nucleus(top_p, min_p, noise_fn)
         plan = self._guidance_plan(texts, cond_scale, guidance_schedule, negative_texts, blend)
         known = None
         if exists(known_ids) or exists(known_mask):
@@ -976,7 +984,7 @@ class Phenaki(PackedModule):
                 if kind == 'gumbel':
                     return L.TorchPhilox(device, shape[0] * shape[1] * shape[2])
                 return torch.zeros(shape, device=device).float().uniform_(0, 1)
-        return plan, known, noise_fn, critic_noise, filter_k
+        return plan, known, noise_fn, critic_noise, filter_k, nucleus
 
     def _filter_k(self, filter_thres, top_k, noise_fn):
         """the k of the top-k filter from sample()'s filter_thres / top_k: None for the plain path (no filter given, or one that keeps all V
@@ -997,6 +1005,26 @@ class Phenaki(PackedModule):
                 raise ValueError(f'sample: filter_thres must be a finite number in [0, 1), got {filter_thres!r}')
             k = max(int((1 - filter_thres) * V), 1)
         return None if k >= V else k
+
+    def _filter_nucleus(self, top_p, min_p, noise_fn):
+        """(top_p, min_p) as floats when sample()'s top_p / min_p make a filter active, else None: top_p None or 1 and min_p None or 0 are off"""
+        if top_p is None and min_p is None:
+            return None
+        number = lambda x: not isinstance(x, bool) and isinstance(x, (int, float))
+        if top_p is not None and not (number(top_p) and 0. < top_p <= 1.):                               # NaN fails the range
+            raise ValueError(f'sample: top_p must be a finite number in (0, 1], got {top_p!r}')
+        if min_p is not None and not (number(min_p) and 0. <= min_p < 1.):
+            raise ValueError(f'sample: min_p must be a finite number in [0, 1), got {min_p!r}')
+        top_p, min_p = 1. if top_p is None else float(top_p), 0. if min_p is None else float(min_p)
+        if top_p == 1. and min_p == 0.:
+            return None
+        if isinstance(noise_fn, str):
+            raise ValueError("sample: top_p / min_p cannot be combined with _noise_fn='torch' (the Philox stream has no filtered path)")
+        # the kernel takes both as f32: what is in range as a double stays in range (and active) as a float.  A top_p below 2^-126 keeps the
+        # maximum alone either way and a min_p above 1 - 2^-24 the maximum's exact ties alone; a positive min_p below 2^-126 is raised to it
+        if min_p > 0.:
+            min_p = min(max(min_p, 2. ** -126), 1. - 2. ** -24)
+        return max(top_p, 2. ** -126), min_p
 
     def _prime_tokens(self, prime_frames, prime_ids, device):
         """(token ids (B, n_prime) of the prime frames, their frame count), (None, 0) without; `prime_ids` (tests) replaces the tokenizer's ids"""
@@ -1055,15 +1083,18 @@ class Phenaki(PackedModule):
         self.__dict__['_pk_last_seed'] = seed_base
         return seed_base
 
-    def _sample_key(self, B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known, filter_k=None):
+    def _sample_key(self, B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known, filter_k=None,
+                    nucleus=None):
         """what a captured graph of the loop depends on (`_pk_sample_graphs`' key, kept in `_pk_last_sample_key`).  On the table path the
         scales, schedule and weights live in the table, a static input refilled per call: the key names the launch structure only --
         ('guided', P, has_negative, L) in place of the scale -- so calls that differ only in those replay one graph.  Infilling: the free
         counts are part of the key; another mask with the same counts replays, other counts capture again.  The resolved k of a top-k filter
-        (None on the plain path) is the last entry: another k is another kernel argument and captures another graph."""
+        (None on the plain path) is the last entry: another k is another kernel argument and captures another graph.  With an active nucleus
+        filter the last entry is ('nucleus', k or None, top_p, min_p) instead."""
         scale = float(cx.cond_scale) if cx.P is None else ('guided', cx.P, cx.has_negative, cx.text_shape[1])
         key = (B, n, n_prime, prime_num_frames, tuple(patch_shape), cx.text_shape, scale, float(starting_temperature), float(noise_K), compact,
-               dt, str(device), self.steps, self.critic_noise_anneal_schedule, None if known is None else tuple(known[2]), filter_k)
+               dt, str(device), self.steps, self.critic_noise_anneal_schedule, None if known is None else tuple(known[2]),
+               filter_k if nucleus is None else ('nucleus', filter_k, float(nucleus[0]), float(nucleus[1])))
         self.__dict__['_pk_last_sample_key'] = key
         return key
 
@@ -1082,9 +1113,9 @@ class Phenaki(PackedModule):
                           scores=[torch.empty((B, n), device=device, dtype=torch.float32) for _ in range(2)],
                           rows=torch.empty((B * n,), device=device, dtype=torch.int32),
                           partials=(torch.empty((5 * L.vocab_ntiles(V) * B * n,), device=device, dtype=torch.float32)
-                                    if scalars.get('filter_k') is None else None),            # the filtered head has the slab instead
+                                    if scalars.get('filter_k') is None and scalars.get('nucleus') is None else None),   # a filtered head has the slab instead
                           mixed=torch.empty((B * n, D), device=device, dtype=L.tdtype(dt)), **scalars)
-        if st.filter_k is not None:
+        if st.filter_k is not None or st.nucleus is not None:
             st.slab = torch.empty((L.filter_slab_rows(B * n, V), V), device=device, dtype=torch.float32)
         if plan is not None:
             st.table = plan['table'].to(device)
@@ -1195,7 +1226,7 @@ class Phenaki(PackedModule):
     def sample(self, *, num_frames, texts=None, prime_frames=None, batch_size=1, cond_scale=3.,
                starting_temperature=0.9, noise_K=1., _noise_fn=None, _trace=None, _return_ids=False, _compact=None, _seed=None,
                _force_fn=None, _prime_ids=None, known_ids=None, known_mask=None, guidance_schedule=None, negative_texts=None, blend=None,
-               filter_thres=None, top_k=None):
+               filter_thres=None, top_k=None, top_p=None, min_p=None):
         """phenaki_pytorch.py:418-560: `num_frames` new frames for `texts` (a str or B strings; without texts `batch_size` samples), continuing
         `prime_frames` if given.  Returns the video (B, C, num_frames, H, W).
 
@@ -1221,6 +1252,15 @@ class Phenaki(PackedModule):
         of a critic-less run stays 1 - p under the unfiltered softmax.  k = V, or neither argument, is the plain path: the logits are never
         formed.  With a filter they are, one (R, V) f32 slab at a time (`_lib.vocab_sample_filtered`).  Not combined with _noise_fn='torch'.
 
+        Nucleus and min-p filtering (the reference has neither).  `top_p`: a finite number in (0, 1], None or 1 = off: keep the smallest set of
+        most likely codes whose probability sums to top_p.  `min_p`: a finite number in [0, 1), None or 0 = off: keep the codes whose
+        probability is at least min_p times the most likely one's.  Either or both may be combined with one of filter_thres / top_k; the
+        filters apply in the order temperature, top-k, top-p, min-p and a column is kept iff every active one keeps it.  The probabilities are
+        those of softmax(logits / T) at the step's annealed temperature T (the distribution the gumbel arg-max samples from), top-p taken on
+        the top-k set's own mass; exact ties at a cut are all kept, and at the last step (T = 0) the nucleus is the row maximum and its exact
+        ties.  The exact arithmetic is pk_logits_nucleus_sample's (include/phenaki_hip.h).  With either active every step's head is one
+        `_lib.vocab_sample_nucleus`; both off is exactly the path above.  Not combined with _noise_fn='torch'.
+
         Shape, dtype, range and length errors (known ids outside [0, num_tokens), a sample with nothing to generate, non-finite values, more
         than two blend entries, a guidance argument without texts or on an unconditional MaskGit, an unknown critic_noise_anneal_schedule)
         are ValueErrors raised before anything launches (`_sample_arguments`).
@@ -1235,9 +1275,9 @@ class Phenaki(PackedModule):
         if isinstance(texts, str):
             texts = [texts]
         B = len(texts) if exists(texts) else batch_size
-        plan, known, noise_fn, critic_noise, filter_k = self._sample_arguments(texts, B, num_frames, prime_frames, cond_scale, guidance_schedule,
-                                                                               negative_texts, blend, known_ids, known_mask, _noise_fn, noise_K,
-                                                                               device, filter_thres, top_k)
+        plan, known, noise_fn, critic_noise, filter_k, nucleus = self._sample_arguments(
+            texts, B, num_frames, prime_frames, cond_scale, guidance_schedule, negative_texts, blend, known_ids, known_mask, _noise_fn, noise_K, device,
+            filter_thres, top_k, top_p, min_p)
         prime_ids, prime_num_frames = self._prime_tokens(prime_frames, _prime_ids, device)
         n_prime = 0 if prime_ids is None else prime_ids.shape[-1]
         n = self.cvivit.num_tokens_per_frames(num_frames, include_first_frame=not exists(prime_frames))
@@ -1247,10 +1287,12 @@ class Phenaki(PackedModule):
         compact = (_trace is None) if _compact is None else bool(_compact)    # traces record the prediction at EVERY position
         if _force_fn is not None:
             compact = False                                                    # the forced mask need not be the top-k one
-        key = self._sample_key(B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known, filter_k)
+        key = self._sample_key(B, n, n_prime, prime_num_frames, patch_shape, cx, starting_temperature, noise_K, compact, dt, device, known, filter_k,
+                               nucleus)
         make_state = partial(self._sample_state, B, n, patch_shape, cx, plan, known, device, dt, n_prime=n_prime, prime_ids=prime_ids,
                              prime_num_frames=prime_num_frames, compact=compact, starting_temperature=starting_temperature,
-                             critic_noise=critic_noise, noise_fn=noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base, filter_k=filter_k)
+                             critic_noise=critic_noise, noise_fn=noise_fn, trace=_trace, force_fn=_force_fn, seed_base=seed_base, filter_k=filter_k,
+                             nucleus=nucleus)
         if self.__dict__.get('_pk_sample_graph', False) and noise_fn is None and _trace is None and _force_fn is None:
             return self._sample_graphed(key, make_state, cx, plan, prime_ids, known, seed_base, _return_ids)
         st = make_state()
