@@ -164,11 +164,14 @@ __global__ __launch_bounds__(256) void bmm_kernel(const float* __restrict__ A, l
 //   l2 x scale   z = x^ sc, x^ = x / |x|;  dx = P t / |x| (t = dz sc, P = I - x^ x^T), dsc = sum_rows dz x^;
 //                second order: grad_dz = sc P gx / |x| + gsc x^,  grad_sc = sum_rows dz P gx / |x|,
 //                              grad_x = -[P (a gx + b t) + x^ <gx, t - x^ a>] / |x|^2 + P (gsc dz) / |x|,  a = <x^, t>, b = <gx, x^>
+//                under F.normalize's clamp (|x| < eps = 1e-12, the zero row included) the normaliser is the constant eps and z = x sc / eps is linear in x:
+//                x^ = x / eps, dx = t / eps, dsc = sum_rows dz x^;  grad_dz = sc gx / eps + gsc x^,  grad_sc = sum_rows dz gx / eps,  grad_x = gsc dz / eps
 //   LayerNorm    dx = (g^ - mean g^ - x^ mean(g^ x^)) / sigma (g^ = dy gamma), dgamma = sum_rows dy x^;
 //                second order (u for dx, w for dgamma): gg = (u - mean u - x^ mean(u x^)) / sigma, grad_dy = gamma gg + w x^, grad_gamma = sum_rows dy gg,
 //                              v = -(m2 u + c2 g^) / sigma + w dy,  grad_x = (v - mean v - x^ mean(v x^)) / sigma - S x^ / (D sigma^2),
 //                              S = <u, g^> - D c1 m1 - D c2 m2,  c1 = mean u, c2 = mean(u x^), m1 = mean g^, m2 = mean(g^ x^)
-// (each checked against torch.autograd on the CPU to 1e-15 before it was written down here, and against torch on the GPU in tests/test_gan_gpu.py)
+// (each is transcribed in float64 and held to torch.autograd in tests/test_gan_kernels_host.py; the kernels are held to the same autograd element by
+// element in tests/test_gan_kernels_gpu.py)
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -218,12 +221,33 @@ __global__ __launch_bounds__(256) void row_l2scale_kernel(const float* __restric
     const float* xr = x + row * d;
     float ss = 0.f;
     for (int j = lane; j < d; j += 64) ss += xr[j] * xr[j];
-    const float nrm = fmaxf(sqrtf(wsum(ss)), 1e-12f), inv = 1.0f / nrm;      // F.normalize eps
+    const float root = sqrtf(wsum(ss)), nrm = fmaxf(root, 1e-12f), inv = 1.0f / nrm;      // F.normalize eps
+    // under the clamp the normaliser is the CONSTANT 1e-12: z = x sc / eps is linear in x, so modes 1 and 2 leave through their own loops below (no
+    // projection, no curvature); every other row runs the expressions it always ran (one wave per row: the branch is uniform)
+    const bool clamped = root < 1e-12f;
     if (mode == 0) {
         for (int j = lane; j < d; j += 64) o0[row * d + j] = xr[j] * inv * sc[j];
         return;
     }
     const float* dzr = dz + row * d;
+    if (mode == 1 && clamped) {
+        for (int j = lane; j < d; j += 64) {
+            const float u = xr[j] * inv, t = dzr[j] * sc[j];
+            o0[row * d + j] = t * inv;
+            o1[row * d + j] = dzr[j] * u;
+        }
+        return;
+    }
+    if (clamped) {
+        const float* gr = gx + row * d;
+        for (int j = lane; j < d; j += 64) {
+            const float u = xr[j] * inv;
+            o2[row * d + j] = sc[j] * gr[j] * inv + gsc[j] * u;              // grad_dz
+            o1[row * d + j] = dzr[j] * gr[j] * inv;                           // grad_sc contribution of this row
+            o0[row * d + j] = gsc[j] * dzr[j] * inv;                          // grad_x
+        }
+        return;
+    }
     float a = 0.f;                                                        // <x^, t>, t = dz sc
     for (int j = lane; j < d; j += 64) a += xr[j] * inv * dzr[j] * sc[j];
     a = wsum(a);
@@ -298,7 +322,9 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-static int conv_out(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+// output positions of a convolution; 0 when the kernel does not fit the padded image (C's division truncates toward zero: (n + 2 pad - k) / stride + 1
+// would call a kernel one short of fitting a single output position, where the caller's floor division gives none)
+static int conv_out(int n, int k, int stride, int pad) { return n + 2 * pad < k ? 0 : (n + 2 * pad - k) / stride + 1; }
 
 extern "C" int pk_im2col(const float* x, int B, int H, int W, int C, int kh, int kw, int stride, int pad, float* cols, long ldc, void* stream) {
     if (!x || !cols || B <= 0 || H <= 0 || W <= 0 || C <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0) return PK_EINVAL;
